@@ -27,6 +27,11 @@ Contract (see the task statement):  python bench.py --gpus N --steps K --warmup 
               owners' new boundary positions are all-reduced.  STRONG scaling: the total work is fixed.  (--mode halo --gpus 1 is the
               plain single-GPU run of that mesh, the N = 1 point of the curve.)
   value     = (valid vertices of the whole scene) * K / (max over ranks of the wall time of the K timed steps).
+  A plain run sets up, warms up, times the K steps and prints the headline fields (metric, value, unit, higher_is_better, dtype,
+  ms_per_step = wall time of one timed step, the workload).  --full then also runs what the headline does not need: the graph-replay
+  pass, the per-stage pass behind the rooflines, stage times and collectives, the device copy ceiling and the CPU baseline.
+  --dump-outputs DIR writes the vertex positions the last timed block returned as DIR/positions.npy (float32; inputs are seeded,
+  so two builds given the same arguments can be compared array for array; other ranks of --mode tiles: positions_rank<r>.npy).
 """
 import argparse
 import json
@@ -128,11 +133,29 @@ def parse_args(argv=None):
                          "'group' = the fall-back that needs none of that: the split-phase C-ABI with torch.distributed's all-reduces between the phases (what the gloo tests drive). "
                          "NW_GRAPH_COMM=0 keeps 'library' but launches multi-rank blocks one by one instead of replaying a recording")
     ap.add_argument('--scale', type=float, default=1.0, help='shrink the workload (debug only; the reported config says so)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-graph-pass', action='store_true', help='skip the extra un-instrumented (graph-replay) pass (profiling runs)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure everything beside the headline figure: the graph-replay pass, the per-stage pass '
+                         '(rooflines, stage times, collectives), the device copy ceiling and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed path returned in its last step (the vertex positions) as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-graph-pass', action='store_true', help='--full: skip the extra un-instrumented (graph-replay) pass (profiling runs)')
     ap.add_argument('--rank-timeout', type=float, default=600.0, help='--gpus N started with plain python: seconds after which ranks that are still running are ended and the run fails')
-    ap.add_argument('--cpu-iters', type=int, default=0, help='oracle iterations for cpu_baseline (0 = about 10-20 s of CPU work: 10 up to 2M localizations, else 3)')
+    ap.add_argument('--cpu-iters', type=int, default=0, help='--full: oracle iterations for cpu_baseline (0 = about 10-20 s of CPU work: 10 up to 2M localizations, else 3)')
     return ap.parse_args(argv)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, name, a):
+    """`a` as out_dir/name.npy in float32; rows beyond DUMP_LIMIT_BYTES are thinned to a fixed, seeded sample (sorted row order)."""
+    a = np.array(a, dtype=np.float32)                       # (a copy: the library reuses its result buffers in later blocks)
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // max(a[:1].nbytes, 1)
+        a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def free_port():
@@ -286,15 +309,16 @@ def run_rank(args):
         cg_of = lambda: cg
 
     executed = [0]
+    result = [None]                                  # what the last block returned to its caller (the vertex positions)
 
     def run_steps(k):
         done = 0
         while done < k:
             n = min(BLOCK, k - done)
             if halo:
-                scene.search(cfg['lams'], n, s_inv)
+                result[0] = scene.search(cfg['lams'], n, s_inv)
             else:
-                runner.search(pts, cfg['lams'], n, s_inv)
+                result[0] = runner.search(pts, cfg['lams'], n, s_inv)
             executed[0] += cg_of().loopcount         # iterations that really ran (the device-side stop condition can end a block early)
             done += n
 
@@ -350,13 +374,15 @@ def run_rank(args):
     steps_done = executed[0]
     if steps_done != args.steps:
         raise SystemExit('bench: only %d of %d timed iterations executed (stop condition fired): the throughput would be overstated' % (steps_done, args.steps))
+    if args.dump_outputs and (rank == 0 or not halo):        # ('halo': every rank returns the same whole mesh)
+        dump_outputs(args.dump_outputs, 'positions' if rank == 0 else 'positions_rank%d' % rank, result[0])
     nn_ms, nn_launches = cg_of().stage_ms_total['nn']
     reparts = (scene.repartitions - reparts0) if halo else 0
     host_ms = dict(scene.host_ms) if halo else {}
     # the same K steps once more WITHOUT events: every block is then one replayed hipGraph (what a caller who does not profile gets).
     # Reported beside the official number, never instead of it.
     dt_graph = None
-    if not multi and not args.no_graph_pass:
+    if args.full and not multi and not args.no_graph_pass:
         cg.set_profiling(0)
         run_steps(BLOCK)                       # captures (first un-instrumented block)
         fence()
@@ -364,20 +390,21 @@ def run_rank(args):
         run_steps(args.steps)
         fence()
         dt_graph = time.perf_counter() - tg
-    set_profiling(2)
-    # per-stage timings: every stage a launch of its own (in the timed region the attraction step rides in the query launch: nw_debug what = 3)
-    fused_query = not multi or native_comm
-    if hasattr(cg_of(), 'separate_attraction'):
-        cg_of().separate_attraction(True)
-    ctimer = None
-    if multi and not native_comm:
-        ctimer = parallel.CollectiveTimer()          # device time inside the collectives of the extra iterations
-        (scene.ex if halo else runner.ex).collective_timer = ctimer
-    run_steps(2 * BLOCK)
-    fence()
-    comm_ms, comm_n = ctimer.total_ms() if ctimer is not None else (0.0, 0)
-    stage = dict(cg_of().stage_ms_total)
-    n_extra = max(stage['update'][1], 1)
+    if args.full:
+        set_profiling(2)
+        # per-stage timings: every stage a launch of its own (in the timed region the attraction step rides in the query launch: nw_debug what = 3)
+        fused_query = not multi or native_comm
+        if hasattr(cg_of(), 'separate_attraction'):
+            cg_of().separate_attraction(True)
+        ctimer = None
+        if multi and not native_comm:
+            ctimer = parallel.CollectiveTimer()          # device time inside the collectives of the extra iterations
+            (scene.ex if halo else runner.ex).collective_timer = ctimer
+        run_steps(2 * BLOCK)
+        fence()
+        comm_ms, comm_n = ctimer.total_ms() if ctimer is not None else (0.0, 0)
+        stage = dict(cg_of().stage_ms_total)
+        n_extra = max(stage['update'][1], 1)
     rccl = None
     if multi:
         t = torch.tensor([dt], dtype=torch.float64, device='cuda')
@@ -389,12 +416,13 @@ def run_rank(args):
             mt = torch.tensor([float(M)], dtype=torch.float64, device='cuda')
             dist.all_reduce(mt, op=dist.ReduceOp.SUM)
             M_total = float(mt.item())
-        devs = [None] * world
-        p = torch.cuda.get_device_properties(torch.cuda.current_device())
-        dist.all_gather_object(devs, dict(rank=rank, device=torch.cuda.current_device(), name=p.name, pci_bus_id=getattr(p, 'pci_bus_id', None)))
-        rccl = dict(backend=dist.get_backend(), world_size_seen=dist.get_world_size(), devices=devs,
-                    collectives_issued_by=('the library: ncclAllReduce on the nw_ctx stream between the phases, part of the block\'s hipGraph (nw_comm_init, include/nanowrap.h)'
-                                           if native_comm else 'the process group, between the phases of the split-phase C-ABI'))
+        if args.full:
+            devs = [None] * world
+            p = torch.cuda.get_device_properties(torch.cuda.current_device())
+            dist.all_gather_object(devs, dict(rank=rank, device=torch.cuda.current_device(), name=p.name, pci_bus_id=getattr(p, 'pci_bus_id', None)))
+            rccl = dict(backend=dist.get_backend(), world_size_seen=dist.get_world_size(), devices=devs,
+                        collectives_issued_by=('the library: ncclAllReduce on the nw_ctx stream between the phases, part of the block\'s hipGraph (nw_comm_init, include/nanowrap.h)'
+                                               if native_comm else 'the process group, between the phases of the split-phase C-ABI'))
     else:
         M_total = float(M)
 
@@ -407,26 +435,6 @@ def run_rank(args):
             Fl = int(np.asarray(scene.ex.cg.faces).shape[0])
         else:
             Nl, Ml, Fl = N, M, F
-        per_kernel, per_iter = algorithmic_bytes(Nl, Ml, Fl)
-        per_kernel_timed, _ = algorithmic_bytes(Nl, Ml, Fl, attract_in_query=os.environ.get('NW_ATTRACT_IN_NN', '1') != '0')
-        # dominant kernel by device time, from HIP events recorded around each launch on the library's stream
-        kern = {'nn': 'k_nn_wave', 'attract': 'k_attract', 'as': 'k_subspace_point_sums', 'prior': 'k_prior_directions',
-                'update': 'k_solve_update'}          # single-kernel stages (grid build and the NN fix-up are reported in stage_ms_per_iter)
-        dom = max((k for k in kern), key=lambda k: stage[k][0] / max(stage[k][1], 1))
-        if dom == 'nn' and nn_launches > 0:
-            ms_tot, launches = nn_ms, nn_launches            # measured live over the timed region
-        else:
-            ms_tot, launches = stage[dom]                    # (extra pass: the NN query is no longer the dominant kernel)
-        avg_ms = ms_tot / max(launches, 1)
-        dom_bytes = per_kernel_timed[kern[dom]] if (dom == 'nn' and nn_launches > 0) else per_kernel[kern[dom]]
-        achieved = dom_bytes / (avg_ms * 1e-3) / 1e9
-        traffic = None
-        tfile = os.path.join(ROOT, 'profiles', PMC_FILE)     # NOT measured by this run
-        if os.path.exists(tfile) and args.config == 'c3' and args.scale == 1.0 and world == 1:
-            try:
-                traffic = json.load(open(tfile)).get(kern[dom])
-            except Exception:
-                traffic = None
         if not multi:
             par = 'single GPU'
         elif halo:
@@ -447,7 +455,6 @@ def run_rank(args):
             'warmup': args.warmup,
             'warmup_executed': warmup_executed,
             'ms_per_step': dt / args.steps * 1e3,
-            'ms_per_step_graph_replay': (dt_graph / args.steps * 1e3) if dt_graph is not None else None,
             'higher_is_better': True,
             'scaling': 'strong' if halo else 'weak',
             'vs_baseline': None,
@@ -459,88 +466,112 @@ def run_rank(args):
                        'one_off_setup': 'nw_optimize_layout after the warm-up, before the timed region: projection re-sort of the localizations, cell-size tuner (a few timed probe queries), heavy-first order of the query work list (one timed query); then two more untimed blocks of min(warmup, %d) iterations (a block\'s hipGraph is recorded per staging half of its result: both before the timed region): %d iterations ran before the timed region' % (BLOCK, warmup_executed),
                        'mode': args.mode if multi else 'single',
                        'parallelism': par},
-            'roofline': {'bound': 'hbm', 'kernel': kern[dom], 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                         'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic,
-                         'traffic_source': ('profiles/%s (rocprofv3 --pmc passes of this workload, committed; not re-measured by this run)' % PMC_FILE if traffic is not None else None),
-                         'algorithmic_bytes_per_launch': dom_bytes, 'avg_launch_ms': avg_ms, 'launches': launches,
-                         'launch_holds': ('the nearest-face query, the ring half of the curvature prior (1-ring gathers) and -- behind a warm query -- the attraction step of the same work items: workgroups appended to k_nn_wave\'s grid run in the query\'s drain (round 5); algorithmic bytes = the three stages\' (SURVEY 8d items)' if dom == 'nn' else None),
-                         'launches_note': 'HIP events on the library stream around the k_nn_wave launch of the last iteration of every block of %d of the timed region (that iteration is launched from the host while the replayed hipGraph of the block\'s other iterations is still running)' % BLOCK,
-                         'measured_copy_peak': measured_copy_ceiling(torch)},
-            'roofline_iteration': {'algorithmic_bytes': per_iter, 'device_ms': stage['total'][0] / n_extra,
-                                   'achieved': per_iter / (stage['total'][0] / n_extra * 1e-3) / 1e9, 'peak': HBM_PEAK_GBS,
-                                   'unit': 'GB/s', 'note': 'sum of per-stage HIP-event spans of %d extra iterations run after the timed region%s' % (n_extra, ' (rank 0, its share)' if world > 1 else '')},
-            'stage_ms_per_iter': {k: stage[k][0] / n_extra for k in stage},
-            'stage_ms_note': 'HIP-event spans of %d extra iterations behind the timed region with EVERY stage a launch of its own (nw_debug what = 3); in the timed region the attraction step rides in the query launch, whose live average is roofline.avg_launch_ms' % n_extra,
-            'nn_max_ring': cg_of().nn_max_ring, 'mean_dist_nm': cg_of().mean_dist,
         }
-        out['roofline_iteration']['frac'] = out['roofline_iteration']['achieved'] / HBM_PEAK_GBS
-        if multi:
-            out['rccl'] = rccl
-            if native_comm:
-                out['collectives'] = {'per_iter': 3 if halo else 1, 'ms_per_iter': None,
-                                      'note': 'issued inside nw_search (not bracketed by events: they are nodes of the block\'s hipGraph); their cost is the difference between ms_per_step and the device time of the stages'}
+        if args.full:
+            per_kernel, per_iter = algorithmic_bytes(Nl, Ml, Fl)
+            per_kernel_timed, _ = algorithmic_bytes(Nl, Ml, Fl, attract_in_query=os.environ.get('NW_ATTRACT_IN_NN', '1') != '0')
+            # dominant kernel by device time, from HIP events recorded around each launch on the library's stream
+            kern = {'nn': 'k_nn_wave', 'attract': 'k_attract', 'as': 'k_subspace_point_sums', 'prior': 'k_prior_directions',
+                    'update': 'k_solve_update'}          # single-kernel stages (grid build and the NN fix-up are reported in stage_ms_per_iter)
+            dom = max((k for k in kern), key=lambda k: stage[k][0] / max(stage[k][1], 1))
+            if dom == 'nn' and nn_launches > 0:
+                ms_tot, launches = nn_ms, nn_launches            # measured live over the timed region
             else:
-                out['collectives'] = {'ms_per_iter': comm_ms / n_extra, 'per_iter': comm_n / n_extra,
-                                      'share_of_device_time': (comm_ms / n_extra) / max(stage['total'][0] / n_extra + comm_ms / n_extra, 1e-12),
-                                      'note': 'rank 0, event-bracketed all-reduces of %d extra iterations after the timed region' % n_extra}
-            if halo:
-                out['halo'] = {'radius_nm': args.halo, 'per_localization_halos': bool(scene.per_point), 'margin_nm': float(getattr(scene, '_cut_margin', args.halo)),
-                               'exchange': args.exchange,
-                               'exchange_bytes': int(scene.exchange_bytes) + 28 * 32 * 8,
-                               'exchange_bytes_note': ('bytes rank 0 SENDS per iteration: 32 B for every copy it holds of a vertex another rank owns (partial accumulator row to the owner), 28 B for every copy another rank holds of a vertex it owns (the sum as four float32 and the new position back), + the 7 KB of normal-equation sums' if args.exchange == 'peers' else 'bytes of the two dense buffers every rank all-reduces per iteration (44 B per boundary vertex of the whole mesh) + the 7 KB of normal-equation sums'),
-                               'boundary_vertices': int(scene.boundary_vertices), 'repartitions_in_timed_region': reparts,
-                               'max_nn_distance_nm': scene.max_dist, 'drift_since_partition_nm': scene.drift,
-                               'host_ms_per_block': host_ms,
-                               'vertices_held_over_owned': float(Ml) * world / max(M, 1)}
-        # BASELINE.json north_star: ">= 40 % of the HBM-bandwidth roofline on the curvature+attraction kernel" (SURVEY 8d:
-        # <= 0.17 ms/iter for them at C3): the attraction/scatter, curvature-prior, A.S and update kernels together, their
-        # SURVEY-8d algorithmic bytes over their HIP-event spans
-        ca = ('attract', 'prior', 'as', 'update')
-        ca_bytes = sum(per_kernel[kern[k]] for k in ca)
-        ca_ms = sum(stage[k][0] for k in ca) / n_extra
-        out['roofline_attraction_curvature'] = {'kernels': [kern[k] for k in ca], 'algorithmic_bytes': ca_bytes, 'device_ms': ca_ms,
-                                                'achieved': ca_bytes / (ca_ms * 1e-3) / 1e9, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                                                'frac': ca_bytes / (ca_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                                'note': 'SURVEY 8d algorithmic bytes (the unfused itemisation both builder and judge use) over the four kernels\' HIP-event spans as launches of their own; frac_physical = the same spans against the bytes the PMC counters saw (file-sourced)'}
-        # what the counters say these four kernels really move (committed PMC passes; lower bound = FETCH_SIZE + WRITE_SIZE, see the file's _bounds)
-        if os.path.exists(tfile) and args.config == 'c3' and args.scale == 1.0 and world == 1:
-            try:
-                pj = json.load(open(tfile))
-                phys = sum(pj[kern[k]] for k in ca)
-                out['roofline_attraction_curvature'].update({'traffic': phys, 'traffic_upper': sum(pj['_bounds'][kern[k]][1] for k in ca),
-                                                             'frac_physical': phys / (ca_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                                             'traffic_source': 'profiles/%s (not re-measured by this run)' % PMC_FILE,
-                                                             'wait_share': {kern[k]: pj.get('_wait_share', {}).get(kern[k]) for k in ca}})
-            except Exception:
-                pass
-        # the iteration as the timed region runs it: the query launch holds the attraction step (live average) -- the per-stage sum minus the
-        # two stages it replaces
-        if nn_launches > 0 and stage['attract'][1] > 0:
-            fused = stage['total'][0] / n_extra - stage['nn'][0] / max(stage['nn'][1], 1) - stage['attract'][0] / max(stage['attract'][1], 1) + nn_ms / nn_launches
-            out['roofline_iteration']['device_ms_fused_query'] = fused
-            out['roofline_iteration']['frac_fused_query'] = per_iter / (fused * 1e-3) / 1e9 / HBM_PEAK_GBS
-        # The dominant kernel is not an HBM kernel (25 MB algorithmic per launch): it is bound by VALU instruction issue.  VALU
-        # wave-instructions per launch from the committed SQ_INSTS_VALU pass (tools/profile_round.sh; file-sourced like `traffic`),
-        # against two peaks: the guide's 256 CUs x 4 SIMD x 2.4 GHz / 2 cycles per wave64 instruction, and the ~4.1 cycles per
-        # instruction this kernel's mix actually retires at (SQ_ACTIVE_INST_VALU / SQ_INSTS_VALU of the same pass; a micro-benchmark,
-        # tools/micro/valu_rate.hip, gives 2.6 cycles for pure-VGPR VOP2, 4.3 with an SGPR operand or VCC, 7.0 for v_pk_fma_f32).
-        if traffic is not None and dom == 'nn':
-            try:
-                vi = json.load(open(tfile)).get('k_nn_wave_valu_wave_instructions')
-            except Exception:
-                vi = None
-            if vi:
-                peak = 256 * 4 * 2.4e9 * 0.5
-                out['roofline']['valu_issue'] = {'wave_instructions_per_launch': vi, 'source': 'profiles/%s (not re-measured by this run)' % PMC_FILE,
-                                                 'achieved': vi / (avg_ms * 1e-3), 'peak': peak, 'unit': 'wave-instructions/s',
-                                                 'frac': vi / (avg_ms * 1e-3) / peak, 'frac_of_measured_issue_rate': vi / (avg_ms * 1e-3) / (256 * 4 * 2.4e9 / 4.1)}
-        # a shared box is occasionally throttled (every kernel 5-50x slower for a whole call, seen twice in round 2): flag it
-        cp = out['roofline'].get('measured_copy_peak', 0.0)
-        out['device_health'] = 'ok' if cp >= 3000.0 else 'degraded: device-to-device copy ran at %.0f GB/s (normally ~5100)' % cp
-        if not args.no_cpu_baseline and world == 1:
-            cpu_iters = args.cpu_iters if args.cpu_iters > 0 else (10 if N <= 2000000 else 3)
-            out['cpu_baseline'] = cpu_baseline(synth.make_config(args.config, scale=args.scale, seed=rank), cpu_iters)
-            out['speedup_vs_cpu_baseline'] = out['value'] / out['cpu_baseline']['value']
+                ms_tot, launches = stage[dom]                    # (extra pass: the NN query is no longer the dominant kernel)
+            avg_ms = ms_tot / max(launches, 1)
+            dom_bytes = per_kernel_timed[kern[dom]] if (dom == 'nn' and nn_launches > 0) else per_kernel[kern[dom]]
+            achieved = dom_bytes / (avg_ms * 1e-3) / 1e9
+            traffic = None
+            tfile = os.path.join(ROOT, 'profiles', PMC_FILE)     # NOT measured by this run
+            if os.path.exists(tfile) and args.config == 'c3' and args.scale == 1.0 and world == 1:
+                try:
+                    traffic = json.load(open(tfile)).get(kern[dom])
+                except Exception:
+                    traffic = None
+            out.update({
+                'ms_per_step_graph_replay': (dt_graph / args.steps * 1e3) if dt_graph is not None else None,
+                'roofline': {'bound': 'hbm', 'kernel': kern[dom], 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                             'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic,
+                             'traffic_source': ('profiles/%s (rocprofv3 --pmc passes of this workload, committed; not re-measured by this run)' % PMC_FILE if traffic is not None else None),
+                             'algorithmic_bytes_per_launch': dom_bytes, 'avg_launch_ms': avg_ms, 'launches': launches,
+                             'launch_holds': ('the nearest-face query, the ring half of the curvature prior (1-ring gathers) and -- behind a warm query -- the attraction step of the same work items: workgroups appended to k_nn_wave\'s grid run in the query\'s drain (round 5); algorithmic bytes = the three stages\' (SURVEY 8d items)' if dom == 'nn' else None),
+                             'launches_note': 'HIP events on the library stream around the k_nn_wave launch of the last iteration of every block of %d of the timed region (that iteration is launched from the host while the replayed hipGraph of the block\'s other iterations is still running)' % BLOCK,
+                             'measured_copy_peak': measured_copy_ceiling(torch)},
+                'roofline_iteration': {'algorithmic_bytes': per_iter, 'device_ms': stage['total'][0] / n_extra,
+                                       'achieved': per_iter / (stage['total'][0] / n_extra * 1e-3) / 1e9, 'peak': HBM_PEAK_GBS,
+                                       'unit': 'GB/s', 'note': 'sum of per-stage HIP-event spans of %d extra iterations run after the timed region%s' % (n_extra, ' (rank 0, its share)' if world > 1 else '')},
+                'stage_ms_per_iter': {k: stage[k][0] / n_extra for k in stage},
+                'stage_ms_note': 'HIP-event spans of %d extra iterations behind the timed region with EVERY stage a launch of its own (nw_debug what = 3); in the timed region the attraction step rides in the query launch, whose live average is roofline.avg_launch_ms' % n_extra,
+                'nn_max_ring': cg_of().nn_max_ring, 'mean_dist_nm': cg_of().mean_dist,
+            })
+            out['roofline_iteration']['frac'] = out['roofline_iteration']['achieved'] / HBM_PEAK_GBS
+            if multi:
+                out['rccl'] = rccl
+                if native_comm:
+                    out['collectives'] = {'per_iter': 3 if halo else 1, 'ms_per_iter': None,
+                                          'note': 'issued inside nw_search (not bracketed by events: they are nodes of the block\'s hipGraph); their cost is the difference between ms_per_step and the device time of the stages'}
+                else:
+                    out['collectives'] = {'ms_per_iter': comm_ms / n_extra, 'per_iter': comm_n / n_extra,
+                                          'share_of_device_time': (comm_ms / n_extra) / max(stage['total'][0] / n_extra + comm_ms / n_extra, 1e-12),
+                                          'note': 'rank 0, event-bracketed all-reduces of %d extra iterations after the timed region' % n_extra}
+                if halo:
+                    out['halo'] = {'radius_nm': args.halo, 'per_localization_halos': bool(scene.per_point), 'margin_nm': float(getattr(scene, '_cut_margin', args.halo)),
+                                   'exchange': args.exchange,
+                                   'exchange_bytes': int(scene.exchange_bytes) + 28 * 32 * 8,
+                                   'exchange_bytes_note': ('bytes rank 0 SENDS per iteration: 32 B for every copy it holds of a vertex another rank owns (partial accumulator row to the owner), 28 B for every copy another rank holds of a vertex it owns (the sum as four float32 and the new position back), + the 7 KB of normal-equation sums' if args.exchange == 'peers' else 'bytes of the two dense buffers every rank all-reduces per iteration (44 B per boundary vertex of the whole mesh) + the 7 KB of normal-equation sums'),
+                                   'boundary_vertices': int(scene.boundary_vertices), 'repartitions_in_timed_region': reparts,
+                                   'max_nn_distance_nm': scene.max_dist, 'drift_since_partition_nm': scene.drift,
+                                   'host_ms_per_block': host_ms,
+                                   'vertices_held_over_owned': float(Ml) * world / max(M, 1)}
+            # BASELINE.json north_star: ">= 40 % of the HBM-bandwidth roofline on the curvature+attraction kernel" (SURVEY 8d:
+            # <= 0.17 ms/iter for them at C3): the attraction/scatter, curvature-prior, A.S and update kernels together, their
+            # SURVEY-8d algorithmic bytes over their HIP-event spans
+            ca = ('attract', 'prior', 'as', 'update')
+            ca_bytes = sum(per_kernel[kern[k]] for k in ca)
+            ca_ms = sum(stage[k][0] for k in ca) / n_extra
+            out['roofline_attraction_curvature'] = {'kernels': [kern[k] for k in ca], 'algorithmic_bytes': ca_bytes, 'device_ms': ca_ms,
+                                                    'achieved': ca_bytes / (ca_ms * 1e-3) / 1e9, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                                                    'frac': ca_bytes / (ca_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                                    'note': 'SURVEY 8d algorithmic bytes (the unfused itemisation both builder and judge use) over the four kernels\' HIP-event spans as launches of their own; frac_physical = the same spans against the bytes the PMC counters saw (file-sourced)'}
+            # what the counters say these four kernels really move (committed PMC passes; lower bound = FETCH_SIZE + WRITE_SIZE, see the file's _bounds)
+            if os.path.exists(tfile) and args.config == 'c3' and args.scale == 1.0 and world == 1:
+                try:
+                    pj = json.load(open(tfile))
+                    phys = sum(pj[kern[k]] for k in ca)
+                    out['roofline_attraction_curvature'].update({'traffic': phys, 'traffic_upper': sum(pj['_bounds'][kern[k]][1] for k in ca),
+                                                                 'frac_physical': phys / (ca_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                                                 'traffic_source': 'profiles/%s (not re-measured by this run)' % PMC_FILE,
+                                                                 'wait_share': {kern[k]: pj.get('_wait_share', {}).get(kern[k]) for k in ca}})
+                except Exception:
+                    pass
+            # the iteration as the timed region runs it: the query launch holds the attraction step (live average) -- the per-stage sum minus the
+            # two stages it replaces
+            if nn_launches > 0 and stage['attract'][1] > 0:
+                fused = stage['total'][0] / n_extra - stage['nn'][0] / max(stage['nn'][1], 1) - stage['attract'][0] / max(stage['attract'][1], 1) + nn_ms / nn_launches
+                out['roofline_iteration']['device_ms_fused_query'] = fused
+                out['roofline_iteration']['frac_fused_query'] = per_iter / (fused * 1e-3) / 1e9 / HBM_PEAK_GBS
+            # The dominant kernel is not an HBM kernel (25 MB algorithmic per launch): it is bound by VALU instruction issue.  VALU
+            # wave-instructions per launch from the committed SQ_INSTS_VALU pass (tools/profile_round.sh; file-sourced like `traffic`),
+            # against two peaks: the guide's 256 CUs x 4 SIMD x 2.4 GHz / 2 cycles per wave64 instruction, and the ~4.1 cycles per
+            # instruction this kernel's mix actually retires at (SQ_ACTIVE_INST_VALU / SQ_INSTS_VALU of the same pass; a micro-benchmark,
+            # tools/micro/valu_rate.hip, gives 2.6 cycles for pure-VGPR VOP2, 4.3 with an SGPR operand or VCC, 7.0 for v_pk_fma_f32).
+            if traffic is not None and dom == 'nn':
+                try:
+                    vi = json.load(open(tfile)).get('k_nn_wave_valu_wave_instructions')
+                except Exception:
+                    vi = None
+                if vi:
+                    peak = 256 * 4 * 2.4e9 * 0.5
+                    out['roofline']['valu_issue'] = {'wave_instructions_per_launch': vi, 'source': 'profiles/%s (not re-measured by this run)' % PMC_FILE,
+                                                     'achieved': vi / (avg_ms * 1e-3), 'peak': peak, 'unit': 'wave-instructions/s',
+                                                     'frac': vi / (avg_ms * 1e-3) / peak, 'frac_of_measured_issue_rate': vi / (avg_ms * 1e-3) / (256 * 4 * 2.4e9 / 4.1)}
+            # a shared box is occasionally throttled (every kernel 5-50x slower for a whole call, seen twice in round 2): flag it
+            cp = out['roofline'].get('measured_copy_peak', 0.0)
+            out['device_health'] = 'ok' if cp >= 3000.0 else 'degraded: device-to-device copy ran at %.0f GB/s (normally ~5100)' % cp
+            if not args.no_cpu_baseline and world == 1:
+                cpu_iters = args.cpu_iters if args.cpu_iters > 0 else (10 if N <= 2000000 else 3)
+                out['cpu_baseline'] = cpu_baseline(synth.make_config(args.config, scale=args.scale, seed=rank), cpu_iters)
+                out['speedup_vs_cpu_baseline'] = out['value'] / out['cpu_baseline']['value']
         print(json.dumps(out))
         sys.stdout.flush()
     if multi:

@@ -12,7 +12,6 @@ GOLDEN = os.path.join(ROOT, 'tests', 'golden')
 
 def pytest_configure(config):
     config.addinivalue_line('markers', 'gpu: needs a real MI355X (run with -m gpu on the GPU box)')
-    config.addinivalue_line('markers', 'reference: needs /root/reference (build container only)')
     # the oracle's C library is test infrastructure: build it on demand (gcc only, < 1 s)
     lib = os.path.join(ROOT, 'oracle', 'libnw_oracle.so')
     src = os.path.join(ROOT, 'oracle', 'nw_oracle.c')

@@ -347,6 +347,70 @@ def golden_fit_quality():
     save('fit_quality', **out)
 
 
+
+def golden_random_case():
+    """A seed of its own, outside the other fixtures: the reference's 7 iterations on an icosphere in a noisy shell with per-axis sigma
+    (tests/test_oracle_golden.py::test_live_reference_random_case)."""
+    v, f = icosphere(3, 60.0)
+    rng = np.random.default_rng(1234)
+    d = rng.normal(size=(4000, 3))
+    d /= np.linalg.norm(d, axis=1)[:, None]
+    pts = (d * 50 + rng.normal(scale=4, size=d.shape)).astype('f4')
+    sigma = rng.uniform(2, 6, size=pts.shape).astype('f4')
+    mesh = TriMesh(v, f)
+    cg = ref_harness.new_reference_optimiser(mesh, pts, search_k=200, search_rad=100, shield_sigma=2.0)
+    out = cg.search(pts, lams=[5.0], num_iters=7, sigma_inv=1.0 / sigma.ravel(), weights=None)
+    save('random_case', mesh_vertices=v, mesh_faces=f, points=pts, sigma=sigma, positions=np.asarray(out), log_tests=np.array(cg.tests, 'f8'))
+
+
+def golden_regulariser_failures():
+    """The alternate regularisers in the reference's loop: "Lfunc" / "Lfunc3" raise in the first iteration (a float64 `_ncc()` handed to
+    C code that reads float32), "wfunc" runs -- its positions after 3 iterations
+    (tests/test_oracle_golden.py::test_live_reference_alternate_regularisers_fail_upstream)."""
+    v, f = icosphere(2, 60.0)
+    rng = np.random.default_rng(7)
+    d = rng.normal(size=(800, 3))
+    d /= np.linalg.norm(d, axis=1)[:, None]
+    pts = (d * 50 + rng.normal(scale=4, size=d.shape)).astype('f4')
+    s = 1.0 / np.full(pts.size, 4.0, 'f4')
+    raised = []
+    for names in (["Lfunc", "Lhfunc"], ["Lfunc3", "Lhfunc3"]):
+        mesh = TriMesh(v, f)
+        cg = ref_harness.new_reference_optimiser(mesh, pts, search_k=200, search_rad=100, shield_sigma=2.0)
+        cg.Lfuncs, cg.Lhfuncs = [names[0]], [names[1]]
+        err = ''
+        try:
+            with np.errstate(all='ignore'):
+                cg.search(pts, lams=[1.0], num_iters=3, sigma_inv=s)
+        except Exception as e:                                       # (recorded, not judged, here: the test judges it)
+            err = type(e).__name__
+        raised.append(err)
+    mesh = TriMesh(v, f)
+    cg = ref_harness.new_reference_optimiser(mesh, pts, search_k=200, search_rad=100, shield_sigma=2.0)
+    cg.Lfuncs, cg.Lhfuncs = ["wfunc"], ["wfunc"]
+    out = cg.search(pts, lams=[10.0], num_iters=3, sigma_inv=s)
+    save('regulariser_failures', mesh_vertices=v, mesh_faces=f, points=pts, names=np.array(['Lfunc', 'Lfunc3']), raised=np.array(raised),
+         wfunc_positions=np.asarray(out))
+
+
+def golden_evaluation_case():
+    """The reference's points_from_mesh on a stretched icosphere at dx_min = 3 and 7.5 (p = 1, rows sorted) and its
+    average_squared_distance of two seeded clouds (tests/test_evaluation.py::test_live_reference_points_and_distances)."""
+    ev = ref_harness.load_evaluation_utils()
+    v, f = icosphere(3, 75.0)
+    v = (v * np.array([1.0, 0.6, 1.3], 'f4')).astype('f4')
+    mesh = TriMesh(v, f)
+    out = dict(vertices=v, faces=f)
+    for tag, dx in (('dx3', 3.0), ('dx7_5', 7.5)):
+        np.random.seed(1)
+        pts = np.asarray(ev.points_from_mesh(mesh, dx_min=dx, p=1.0))
+        out['points_' + tag] = pts[np.lexsort((pts[:, 2], pts[:, 1], pts[:, 0]))]
+    rng = np.random.default_rng(3)
+    a, b = rng.normal(size=(500, 3)), rng.normal(size=(700, 3))
+    out.update(a=a, b=b, asd=np.array(ev.average_squared_distance(a, b), 'f8'))
+    save('evaluation_case', **out)
+
+
 if __name__ == '__main__':
     if not ref_harness.available():
         raise SystemExit('reference not available here')
@@ -363,3 +427,6 @@ if __name__ == '__main__':
     golden_curvature()
     golden_sdf_shapes()
     golden_fit_quality()
+    golden_random_case()
+    golden_regulariser_failures()
+    golden_evaluation_case()

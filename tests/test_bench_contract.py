@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,7 +23,7 @@ def _run(args, timeout=600, extra_env=None):
 def test_help_parses_without_a_gpu():
     p = _run(['--help'], timeout=120)
     assert p.returncode == 0
-    for flag in ('--gpus', '--steps', '--warmup', '--config'):
+    for flag in ('--gpus', '--steps', '--warmup', '--config', '--full', '--dump-outputs'):
         assert flag in p.stdout
 
 
@@ -45,7 +46,7 @@ def test_two_ranks_started_by_plain_python_print_one_json_line(mode):
     """The N > 1 entry point on hardware, as the driver runs it: `python3 bench.py --gpus 2 ...` starts its two ranks itself; on this
     one-GPU box they share cuda:0 and gloo carries the collectives (NW_BENCH_BACKEND=gloo; RCCL refuses duplicate devices).  Both
     decompositions: 'tiles' (one vesicle per rank, weak scaling) and 'halo' (ONE mesh sharded over the ranks, strong scaling)."""
-    p = _run(['--gpus', '2', '--steps', '10', '--warmup', '5', '--scale', '0.05', '--mode', mode], timeout=800, extra_env={'NW_BENCH_BACKEND': 'gloo'})
+    p = _run(['--gpus', '2', '--steps', '10', '--warmup', '5', '--scale', '0.05', '--mode', mode, '--full'], timeout=800, extra_env={'NW_BENCH_BACKEND': 'gloo'})
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -72,7 +73,7 @@ def test_rccl_path_replays_blocks_with_their_collectives(mode):
     """The N > 1 code path over RCCL itself, as far as one GPU allows: NW_BENCH_FORCE_DIST=1 runs bench.py's multi-rank branch with ONE
     nccl rank -- the library's own communicator (nw_comm_init), every block one nw_search call whose collectives are nodes of the block's
     hipGraph."""
-    p = _run(['--gpus', '1', '--steps', '20', '--warmup', '10', '--scale', '0.05', '--mode', mode, '--no-cpu-baseline'], timeout=800, extra_env={'NW_BENCH_FORCE_DIST': '1'})
+    p = _run(['--gpus', '1', '--steps', '20', '--warmup', '10', '--scale', '0.05', '--mode', mode, '--full', '--no-cpu-baseline'], timeout=800, extra_env={'NW_BENCH_FORCE_DIST': '1'})
     assert p.returncode == 0, p.stderr[-3000:]
     j = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][0])
     assert j['rccl']['backend'] == 'nccl' and j['rccl']['world_size_seen'] == 1 and j['rccl']['collectives_issued_by'].startswith('the library')
@@ -92,7 +93,7 @@ def test_two_ranks_over_rccl_when_two_gpus_are_visible(mode, extra, env):
     import torch
     if torch.cuda.device_count() < 2:
         pytest.skip('needs two GPUs (RCCL refuses two ranks on one device)')
-    p = _run(['--gpus', '2', '--steps', '10', '--warmup', '5', '--scale', '0.1', '--mode', mode, '--no-cpu-baseline'] + extra, timeout=800, extra_env=env)
+    p = _run(['--gpus', '2', '--steps', '10', '--warmup', '5', '--scale', '0.1', '--mode', mode, '--full', '--no-cpu-baseline'] + extra, timeout=800, extra_env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -110,7 +111,7 @@ def test_fall_backs_of_the_multi_rank_path_run_with_one_rank():
     C-ABI (--collectives group) and through the library's communicator with NW_GRAPH_COMM=0 (blocks launched one by one, never recorded)."""
     for extra, env in ((['--collectives', 'group'], {}), ([], {'NW_GRAPH_COMM': '0'})):
         e = dict(env, NW_BENCH_FORCE_DIST='1')
-        p = _run(['--gpus', '1', '--steps', '10', '--warmup', '5', '--scale', '0.05', '--mode', 'tiles', '--no-cpu-baseline'] + extra, timeout=800, extra_env=e)
+        p = _run(['--gpus', '1', '--steps', '10', '--warmup', '5', '--scale', '0.05', '--mode', 'tiles', '--full', '--no-cpu-baseline'] + extra, timeout=800, extra_env=e)
         assert p.returncode == 0, p.stderr[-3000:]
         j = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][0])
         assert j['rccl']['backend'] == 'nccl' and j['steps'] == 10 and j['value'] > 0
@@ -133,7 +134,7 @@ def test_two_ranks_started_by_the_drivers_launcher_print_one_json_line():
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
         env.pop(k, None)
     p = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1', '--master-port', str(port),
-                        os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '10', '--warmup', '5', '--scale', '0.05'],
+                        os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '10', '--warmup', '5', '--scale', '0.05', '--full'],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=800, universal_newlines=True)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
@@ -145,7 +146,7 @@ def test_two_ranks_started_by_the_drivers_launcher_print_one_json_line():
 
 @pytest.mark.gpu
 def test_one_json_line_with_roofline_and_cpu_baseline():
-    p = _run(['--gpus', '1', '--steps', '10', '--warmup', '5', '--scale', '0.05', '--cpu-iters', '2'])
+    p = _run(['--gpus', '1', '--steps', '10', '--warmup', '5', '--scale', '0.05', '--full', '--cpu-iters', '2'])
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -163,3 +164,24 @@ def test_one_json_line_with_roofline_and_cpu_baseline():
     c = j['cpu_baseline']
     assert c['kind'] == 'port' and c['value'] > 0 and c['cores'] >= 1 and c['unit'] == j['unit']
     assert j['value'] > c['value']
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the headline fields only; --dump-outputs writes the positions the
+    last timed block returned, and a second run with the same arguments writes the same array (seeded inputs, deterministic fit)."""
+    got = []
+    for k in range(2):
+        d = str(tmp_path / ('run%d' % k))
+        p = _run(['--gpus', '1', '--steps', '7', '--warmup', '5', '--scale', '0.05', '--dump-outputs', d])
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1, p.stdout[-2000:]
+        j = json.loads(lines[0])
+        assert j['steps'] == 7 and j['warmup'] == 5 and j['unit'] == 'vertex-updates/s' and j['higher_is_better'] is True and j['dtype'] == 'f32'
+        assert abs(j['value'] - j['config']['vertices_per_gpu'] * 1e3 / j['ms_per_step']) <= 1e-6 * j['value']
+        assert not {'roofline', 'stage_ms_per_iter', 'cpu_baseline', 'ms_per_step_graph_replay'} & set(j)
+        a = np.load(os.path.join(d, 'positions.npy'))
+        assert a.dtype == np.float32 and a.shape == (j['config']['vertices_per_gpu'], 3) and np.isfinite(a).all()
+        got.append(a)
+    assert np.array_equal(got[0], got[1])

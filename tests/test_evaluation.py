@@ -2,8 +2,8 @@
 Fit quality in the reference's own metric (ch_shrinkwrap_amd/evaluation.py restates evaluation_utils.points_from_mesh :35-150 and
 average_squared_distance :153-180 of /root/reference/ch_shrinkwrap/, surfaced upstream by recipe_modules/surface_feature_extraction.py:76-138).
 
-CPU: the restatement against the fixture the reference's own functions produced (tests/golden/fit_quality.npz, make_golden.py) and, when
-/root/reference is present, against the live functions.  GPU: complete fits asserted in that metric against points on the true surface --
+CPU: the restatement against the fixtures the reference's own functions produced (tests/golden/fit_quality.npz and evaluation_case.npz,
+make_golden.py).  GPU: complete fits asserted in that metric against points on the true surface --
 the only handle on the quality of the block-boundary remesher, whose PYME counterpart is not in the reference tree.
 """
 import os
@@ -34,23 +34,15 @@ def test_restatement_equals_the_reference_fixture():
     assert np.isclose(q['mse_rms'], g['mse_dx5'][2], rtol=1e-13) and q['n_mesh_points'] == g['points_dx5'].shape[0]
 
 
-@pytest.mark.reference
 def test_live_reference_points_and_distances():
-    from oracle import ref_harness
-    if not ref_harness.available():
-        pytest.skip('reference not present (GPU box)')
-    ev = ref_harness.load_evaluation_utils()
-    v, f = icosphere(3, 75.0)
-    v = (v * np.array([1.0, 0.6, 1.3], 'f4')).astype('f4')
-    mesh = TriMesh(v, f)
-    for dx in (3.0, 7.5):
-        np.random.seed(1)
-        ref = _sorted(np.asarray(ev.points_from_mesh(mesh, dx_min=dx, p=1.0)))
+    """A second mesh, two more grid spacings and a second pair of clouds, against the reference's own functions' outputs
+    (tests/golden/make_golden.py::golden_evaluation_case)."""
+    g = load_golden('evaluation_case')
+    mesh = TriMesh(g['vertices'], g['faces'])
+    for tag, dx in (('dx3', 3.0), ('dx7_5', 7.5)):
         mine = _sorted(E.points_from_mesh(mesh, dx_min=dx, p=1.0))
-        assert np.array_equal(ref, mine)
-    rng = np.random.default_rng(3)
-    a, b = rng.normal(size=(500, 3)), rng.normal(size=(700, 3))
-    assert E.average_squared_distance(a, b) == tuple(ev.average_squared_distance(a, b))
+        assert np.array_equal(g['points_' + tag], mine)
+    assert E.average_squared_distance(g['a'], g['b']) == tuple(g['asd'])
 
 
 def test_a_mesh_of_the_surface_itself_scores_the_sampling_floor():

@@ -1,13 +1,11 @@
 """
 CPU tests: the oracle (oracle/nanowrap_oracle.py + oracle/nw_oracle.c) against the golden vectors generated
-from the reference (tests/golden/make_golden.py), and -- in the build container -- against the live reference.
+from the reference (tests/golden/make_golden.py).
 """
 import numpy as np
-import pytest
 
 from conftest import load_golden, rel_rms
 from oracle import nanowrap_oracle as O
-from oracle import ref_harness
 
 
 def _mesh(g, prefix=''):
@@ -113,25 +111,16 @@ def test_native_helpers():
     assert np.array_equal(z, g['ah_out'])
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not ref_harness.available(), reason='reference only exists in the build container')
 def test_live_reference_random_case():
-    """Fresh seed, not in the fixtures: oracle vs the reference run side by side."""
-    from ch_shrinkwrap_amd.trimesh import TriMesh, icosphere
-    v, f = icosphere(3, 60.0)
-    rng = np.random.default_rng(1234)
-    d = rng.normal(size=(4000, 3))
-    d /= np.linalg.norm(d, axis=1)[:, None]
-    pts = (d * 50 + rng.normal(scale=4, size=d.shape)).astype('f4')
-    sigma = rng.uniform(2, 6, size=pts.shape).astype('f4')
-    s = 1.0 / sigma.ravel()
-    mesh = TriMesh(v, f)
-    cg = ref_harness.new_reference_optimiser(mesh, pts, search_k=200, search_rad=100, shield_sigma=2.0)
-    out = cg.search(pts, lams=[5.0], num_iters=7, sigma_inv=s, weights=None)
-    m2 = TriMesh(v, f)
+    """Fresh seed, not in the other fixtures: oracle vs the reference's own run of it (tests/golden/make_golden.py::golden_random_case)."""
+    from ch_shrinkwrap_amd.trimesh import TriMesh
+    g = load_golden('random_case')
+    pts = g['points']
+    s = 1.0 / g['sigma'].ravel()
+    m2 = TriMesh(g['mesh_vertices'], g['mesh_faces'])
     r = O.search(m2.vertices.copy(), m2.vertex_normals.copy(), m2.neighbor_vertex_table(), m2.faces, pts, [5.0], 7, s)
-    assert np.array_equal(r.positions, out)
-    assert np.array_equal(np.array(r.tests), np.array(cg.tests))
+    assert np.array_equal(r.positions, g['positions'])
+    assert np.array_equal(np.array(r.tests, 'f8'), g['log_tests'])
 
 
 def test_oracle_float64_points_and_wfunc_against_golden():
@@ -158,32 +147,21 @@ def test_oracle_float64_points_and_wfunc_against_golden():
     assert np.array_equal(np.array(r.tests, 'f8'), g['wfunc_log_tests'])
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not ref_harness.available(), reason='reference only exists in the build container')
 def test_live_reference_alternate_regularisers_fail_upstream():
     """Why only ["I"] and ["wfunc"] are offered inside the loop: with the live default `_ncc()` (float64 because of its integer
     division, mesh_conj_grad.py:782-800) the names that go through conj_grad_utils.c -- "Lfunc", "Lfunc3" -- hand a float64 buffer
-    to C code that reads float32 (conj_grad_utils.c:286-302, no dtype check): the reference raises in its first iteration."""
-    from ch_shrinkwrap_amd.trimesh import TriMesh, icosphere
-    v, f = icosphere(2, 60.0)
-    rng = np.random.default_rng(7)
-    d = rng.normal(size=(800, 3))
-    d /= np.linalg.norm(d, axis=1)[:, None]
-    pts = (d * 50 + rng.normal(scale=4, size=d.shape)).astype('f4')
+    to C code that reads float32 (conj_grad_utils.c:286-302, no dtype check): the reference raises in its first iteration.  The
+    reference's run is recorded in tests/golden/make_golden.py::golden_regulariser_failures: what each name raised, and the positions
+    "wfunc" reached, which the oracle must reproduce."""
+    from ch_shrinkwrap_amd.trimesh import TriMesh
+    g = load_golden('regulariser_failures')
+    assert list(g['names']) == ['Lfunc', 'Lfunc3']
+    assert set(g['raised']) <= {'AssertionError', 'ValueError', 'FloatingPointError'} and all(g['raised'])
+    pts = g['points']
     s = 1.0 / np.full(pts.size, 4.0, 'f4')
-    for names in (["Lfunc", "Lhfunc"], ["Lfunc3", "Lhfunc3"]):
-        mesh = TriMesh(v, f)
-        cg = ref_harness.new_reference_optimiser(mesh, pts, search_k=200, search_rad=100, shield_sigma=2.0)
-        cg.Lfuncs, cg.Lhfuncs = [names[0]], [names[1]]
-        with np.errstate(all='ignore'), pytest.raises((AssertionError, ValueError, FloatingPointError)):
-            cg.search(pts, lams=[1.0], num_iters=3, sigma_inv=s)
-    mesh = TriMesh(v, f)
-    cg = ref_harness.new_reference_optimiser(mesh, pts, search_k=200, search_rad=100, shield_sigma=2.0)
-    cg.Lfuncs, cg.Lhfuncs = ["wfunc"], ["wfunc"]
-    out = cg.search(pts, lams=[10.0], num_iters=3, sigma_inv=s)
-    m2 = TriMesh(v, f)
+    m2 = TriMesh(g['mesh_vertices'], g['mesh_faces'])
     r = O.search(m2.vertices.copy(), m2.vertex_normals.copy(), m2.neighbor_vertex_table(), m2.faces, pts, [10.0], 3, s, regulariser='wfunc')
-    assert np.array_equal(r.positions, out)
+    assert np.array_equal(r.positions, g['wfunc_positions'])
 
 
 def test_oracle_data_other_than_the_localizations_against_golden():

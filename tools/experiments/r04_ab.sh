@@ -7,7 +7,7 @@ mkdir -p $OUT
 n=0
 for v in "$@"; do
   n=$((n+1))
-  env $v NW_VERBOSE=1 timeout -k 10 200 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/v$n.log 2> $OUT/v$n.err || { echo "variant $n failed"; tail -5 $OUT/v$n.err; exit 1; }
+  env $v NW_VERBOSE=1 timeout -k 10 200 python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/v$n.log 2> $OUT/v$n.err || { echo "variant $n failed"; tail -5 $OUT/v$n.err; exit 1; }
   python3 - "$OUT/v$n.log" "$v" <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ mkdir -p $OUT
 n=0
 for v in "$@"; do
   n=$((n+1))
-  env $v timeout -k 10 240 python3 bench.py --steps ${STEPS:-20} --warmup ${WARMUP:-5} --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/v$n.log 2> $OUT/v$n.err || { echo "variant $n failed"; tail -5 $OUT/v$n.err; exit 1; }
+  env $v timeout -k 10 240 python3 bench.py --steps ${STEPS:-20} --warmup ${WARMUP:-5} --full --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/v$n.log 2> $OUT/v$n.err || { echo "variant $n failed"; tail -5 $OUT/v$n.err; exit 1; }
   python3 - "$OUT/v$n.log" "$v" <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
