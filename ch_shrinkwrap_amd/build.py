@@ -1,6 +1,7 @@
 """
 Builds the native pieces in-tree (no pip, no JIT cache):
-  * ch_shrinkwrap_amd/libnanowrap_hip.so  -- the HIP kernels + C-ABI (hipcc, --offload-arch=gfx950): csrc/nanowrap.hip, nw_sort.hip, nw_remesh_dev.hip
+  * ch_shrinkwrap_amd/libnanowrap_hip.so  -- the HIP kernels + C-ABI (hipcc, --offload-arch=gfx950): csrc/nanowrap.hip, nw_sort.hip, nw_remesh_dev.hip,
+                                            nw_holepunch.hip (include/nw_holepunch.h)
   * ch_shrinkwrap_amd/libnw_remesh.so     -- the block-boundary remesher (host C++, g++; include/nw_remesh.h)
 The oracle (test infrastructure) is built by oracle/Makefile, see __graft_entry__.build().
 """
@@ -15,9 +16,12 @@ OBJ_SORT = os.path.join(HERE, 'csrc', 'nw_sort.o')
 OBJ_MAIN = os.path.join(HERE, 'csrc', 'nanowrap.o')
 SRC_REMESH = os.path.join(HERE, 'csrc', 'nw_remesh_dev.hip')   # the block-boundary remesher as kernels (hipCUB scans), its own translation unit
 OBJ_REMESH = os.path.join(HERE, 'csrc', 'nw_remesh_dev.o')
+SRC_HOLEPUNCH = os.path.join(HERE, 'csrc', 'nw_holepunch.hip')  # the hole-punch point queries (include/nw_holepunch.h), its own translation unit
+OBJ_HOLEPUNCH = os.path.join(HERE, 'csrc', 'nw_holepunch.o')
+HDR_HOLEPUNCH = os.path.join(os.path.dirname(HERE), 'include', 'nw_holepunch.h')
 import glob
 # every header of csrc/ is included by nanowrap.hip (directly or through nw_kernels.h): editing any of them must rebuild the library
-DEPS = [SRC, SRC_SORT, SRC_REMESH] + sorted(glob.glob(os.path.join(HERE, 'csrc', '*.h'))) + [os.path.join(os.path.dirname(HERE), 'include', 'nanowrap.h')]
+DEPS = [SRC, SRC_SORT, SRC_REMESH, SRC_HOLEPUNCH, HDR_HOLEPUNCH] + sorted(glob.glob(os.path.join(HERE, 'csrc', '*.h'))) + [os.path.join(os.path.dirname(HERE), 'include', 'nanowrap.h')]
 
 # -ffp-contract=off : the parity-critical float32 arithmetic must round products before adding, exactly like
 #                     the NumPy reference (explicit fma() is used where contraction is wanted);
@@ -48,9 +52,13 @@ def build_hip_library(force=False, verbose=False):
     if force or not os.path.exists(OBJ_REMESH) or os.path.getmtime(OBJ_REMESH) < max(os.path.getmtime(SRC_REMESH), os.path.getmtime(DEPS[-1])):
         run([hipcc, '-O3', '--offload-arch=gfx950', '-fPIC', '-fvisibility=hidden', '-ffp-contract=off', '-Wall', '-Wno-unused-value', '-Wno-unused-function',
              '-c', '-o', OBJ_REMESH, SRC_REMESH])
+    if force or not os.path.exists(OBJ_HOLEPUNCH) or os.path.getmtime(OBJ_HOLEPUNCH) < max(os.path.getmtime(SRC_HOLEPUNCH), os.path.getmtime(HDR_HOLEPUNCH)):
+        # (-ffp-contract=off: the pairing kernel must round every product as the reference's C loop does -- its result is bit-identical)
+        run([hipcc, '-O3', '--offload-arch=gfx950', '-fPIC', '-fvisibility=hidden', '-ffp-contract=off', '-Wall', '-Wno-unused-function',
+             '-c', '-o', OBJ_HOLEPUNCH, SRC_HOLEPUNCH])
     run([hipcc] + [f for f in HIPCC_FLAGS if f != '-shared'] + ['-c', '-o', OBJ_MAIN, SRC])
     check_kernel_budgets(verbose=verbose)          # before the link: a kernel that spills or outgrows its occupancy never ships
-    run([hipcc, '--offload-arch=gfx950', '-fPIC', '-shared', '-o', LIB, OBJ_MAIN, OBJ_SORT, OBJ_REMESH])
+    run([hipcc, '--offload-arch=gfx950', '-fPIC', '-shared', '-o', LIB, OBJ_MAIN, OBJ_SORT, OBJ_REMESH, OBJ_HOLEPUNCH])
     return LIB
 
 
@@ -72,14 +80,32 @@ KERNEL_BUDGETS = {
     'k_prior_directions':             (96, 1024),          # streaming since the ring half left it: 5 waves per SIMD
     'k_subspace_point_sums':          (128, 1024),         # 4 waves per SIMD cover the launch in one round (rows of two localizations in flight)
     'k_solve_update':                 (128, 1024),
+    # hole punching (csrc/nw_holepunch.o): block-boundary queries, budgeted for zero scratch and against silent growth
+    'k_hp_empty_faces':               (64, 0),
+    'k_hp_pair':                      (64, 8 * 1024),      # two LDS tiles of 256 float4 (centroids, normals)
+    'k_hp_prism':                     (176, 0),            # six float64 half-planes and two centres live across the cell walk (3 waves per SIMD)
+    'k_hp_cell_count':                (32, 0),
+    'k_hp_scatter':                   (32, 0),
+    'k_hp_scan_final':                (64, 1024),
+    'k_hp_scan_tiles':                (32, 1024),
+    'k_hp_scan_bsums':                (64, 1024),
+    'k_hp_bbox':                      (32, 0),
+    'k_hp_cand_geom':                 (32, 0),
+    'k_hp_pair_final':                (16, 0),
 }
+BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH]
 
 
 def kernel_resources(obj=None):
-    """{demangled kernel name: {'vgpr', 'sgpr', 'scratch', 'lds', 'vgpr_spill', 'sgpr_spill'}} of the gfx950 code object inside `obj`."""
+    """{demangled kernel name: {'vgpr', 'sgpr', 'scratch', 'lds', 'vgpr_spill', 'sgpr_spill'}} of the gfx950 code object inside `obj`
+    (default: every object of BUDGETED_OBJECTS, merged)."""
     import re
     import tempfile
-    obj = obj or OBJ_MAIN
+    if obj is None:
+        out = {}
+        for o in BUDGETED_OBJECTS:
+            out.update(kernel_resources(o))
+        return out
     with tempfile.TemporaryDirectory() as td:
         fat, co = os.path.join(td, 'fat.bin'), os.path.join(td, 'dev.co')
         subprocess.check_call(['objcopy', '-O', 'binary', '--only-section=.hip_fatbin', obj, fat])

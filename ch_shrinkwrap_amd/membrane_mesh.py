@@ -12,7 +12,8 @@ optimiser per block, the post-block normal refresh, the remesh target-length sch
 PYME's part is the topology surgery at block boundaries -- `remesh`, the deletion half of `remove_necks`,
 `punch_holes`, `remove_extra_short_edges`: they are hooks (`remesher`, `neck_remover`, `hole_puncher`, `edge_cleaner`).
 For `remesh` this package ships its own implementation of the published algorithm (`remesher='builtin'`, remesh.py /
-csrc/remesh.cpp); when no hook is installed the topology is held fixed and that is logged once.  The numerical path of every block is the HIP library; there is no CPU fallback.
+csrc/remesh.cpp); when no hook is installed the topology is held fixed and that is logged once.
+`punch_holes` is defined upstream itself (:877-1199) and is mirrored here (`hole_puncher='device'`: holepunch.py, csrc/nw_holepunch.hip).  The numerical path of every block is the HIP library; there is no CPU fallback.
 """
 import math
 import os
@@ -58,18 +59,31 @@ class MembraneMesh(TriMesh):
         # block-boundary topology hooks (PYME's job in the reference; see module docstring)
         self.remesher = None          # None | 'builtin' (host C++) | 'device' (GPU) | callable(mesh, n, target_edge_length, l, n_relax)
         self.neck_remover = None      # callable(mesh, vertex_ids): delete + repair + remesh (PYME's part of remove_necks)
-        self.hole_puncher = None      # callable(mesh, points, eps)
+        self.hole_puncher = None      # None (no punching) | 'device' (punch_holes: point queries on the GPU) | callable(mesh, points, eps)
         self.edge_cleaner = None      # callable(mesh)  (remove_extra_short_edges)
         self._device = device
         self._native = None
         self._warned_fixed_topology = False
         self.block_log = []
         self.neck_log = []
+        self.punch_log = []
+        self._holepunch = None        # HolePunchContext of the fit (the localizations' cell grid lives on the device beside _native's)
+        self._holepunch_key = None
         self._initialize_curvature_vectors()
         for key, value in kwargs.items():                # :119-120
             setattr(self, key, value)
 
     # -- topology hooks ---------------------------------------------------------------------------------------
+    @property
+    def hole_puncher(self):
+        return self.__dict__.get('_hole_puncher')
+
+    @hole_puncher.setter
+    def hole_puncher(self, value):
+        if not (value is None or value == 'device' or (callable(value) and not isinstance(value, str))):
+            raise ValueError("hole_puncher must be None, 'device' or a callable(mesh, points, eps)")
+        self.__dict__['_hole_puncher'] = value
+
     def _topology_changed(self, vertices, faces, all_referenced=False, mean_edge=None):
         """Rebuild the half-edge tables for a new (vertices, faces) pair; the optimiser of the old topology is dropped."""
         props, vprops = self.vertex_properties, self.vertex_vector_properties
@@ -123,6 +137,92 @@ class MembraneMesh(TriMesh):
             self.cg = None
             self._host_mesh_changed()
         return verts
+
+    # -- hole punching (_membrane_mesh.pyx:877-1199): steps 1-3 on the GPU, 4-6 on the host over the candidates ------------------
+    def _holepunch_context(self, points=None):
+        from .holepunch import HolePunchContext
+        if self._holepunch is None:
+            self._holepunch = HolePunchContext(self._device)
+        if points is not None:
+            key = (id(points), np.shape(points), np.asarray(points).__array_interface__['data'][0])
+            if self._holepunch_key != key:                  # (once per fit: opt_conjugate_gradient forgets the key)
+                self._holepunch.set_points(points)
+                self._holepunch_key = key
+        return self._holepunch
+
+    def _holepunch_mesh_arrays(self):
+        return (np.ascontiguousarray(self.vertices, np.float32), np.ascontiguousarray(self.faces, np.int32),
+                np.ascontiguousarray(self._faces['normal'], np.float32))
+
+    def _holepunch_find_candidate_faces(self, points, eps=10.0):
+        """:877-887: every face with no localization within eps of its centroid, ascending face id (all faces of the mirror are live)."""
+        pos, faces, _ = self._holepunch_mesh_arrays()
+        far = self._holepunch_context(points).empty_faces(pos, faces, eps)
+        return np.flatnonzero(far).astype('i4')
+
+    def _holepunch_pair_candidate_faces(self, candidates):
+        """:897-910 (the C branch): (candidates that found a pair, their pair as an index into that list)."""
+        from .holepunch import pair_postprocess
+        candidates = np.asarray(candidates, 'i4')
+        pairs = self._holepunch_context().pair_faces(*self._holepunch_mesh_arrays(), candidates)
+        return pair_postprocess(candidates, pairs)
+
+    def _holepunch_empty_prism_candidate_faces(self, points, candidates, candidate_pair, eps=10.0):
+        """:946-1016: the pairs whose prism holds no localization, greedily made one-to-one; (faces, index of each one's partner)."""
+        from .holepunch import prism_greedy
+        candidates = np.asarray(candidates, 'i4')
+        empty = self._holepunch_context(points).prism_empty(*self._holepunch_mesh_arrays(), candidates, candidate_pair, eps)
+        return prism_greedy(candidates, np.asarray(candidate_pair), empty)
+
+    def _holepunch_connect_candidates(self, candidates):
+        from .holepunch import connect_candidates
+        return connect_candidates(candidates, self._halfedges['twin'])
+
+    def _holepunch_component_euler_characteristic(self, candidates, component):
+        from .holepunch import component_euler_characteristic
+        return component_euler_characteristic(candidates, component, np.asarray(self.faces))
+
+    def _holepunch_update_topology(self, candidates, candidate_pairs, component, euler):
+        """:1082-1126.  Returns (holes punched, [(component, reason)] of the skips); the mesh is rebuilt once, after all punches."""
+        from .holepunch import plan_punches, apply_punches
+        pos = np.ascontiguousarray(self.vertices, np.float32)
+        faces = np.ascontiguousarray(self.faces, np.int32)
+        plan, skips = plan_punches(pos, faces, self._halfedges['twin'], candidates, candidate_pairs, component, euler,
+                                   region_faces=getattr(self, '_holepunch_region_faces', None))
+        if plan:
+            v, f = apply_punches(pos, faces, plan)
+            self._topology_changed(v, f, all_referenced=True)
+            self.cg = None
+            self._host_mesh_changed()
+        return len(plan), skips
+
+    def punch_holes(self, pts, eps=10.0):
+        """:1163-1199: open holes between opposite face patches with no localization within eps of the prism between them.
+        Every call appends a record to `punch_log`."""
+        log = dict(iteration=getattr(self, '_punch_iteration', None), candidates=0, pairs=0, kept_pairs=0, components=0, chi=[], holes=0, skips=[])
+        self.punch_log.append(log)
+        if not getattr(self, '_in_fit', False):
+            self._holepunch_key = None          # (outside a fit the localizations may be a new array at an old address: the grid is laid again)
+        hc = self._holepunch_find_candidate_faces(pts, eps=eps)
+        log['candidates'] = int(len(hc))
+        if len(hc) < 1:
+            return
+        cands, pairs = self._holepunch_pair_candidate_faces(hc)
+        log['pairs'] = int(len(cands))
+        empty_cands, empty_pairs = self._holepunch_empty_prism_candidate_faces(pts, cands, pairs, eps=eps)
+        log['kept_pairs'] = int(len(empty_cands) // 2)
+        if len(empty_cands) < 1:
+            return
+        component = self._holepunch_connect_candidates(empty_cands)
+        chi = self._holepunch_component_euler_characteristic(empty_cands, component)
+        log['components'], log['chi'] = int(len(chi)), [int(x) for x in chi]
+        self._holepunch_region_faces = hc       # (the surgery cuts the empty region a component lies in: plan_punches)
+        try:
+            holes, skips = self._holepunch_update_topology(empty_cands, empty_pairs, component, chi)
+        finally:
+            self._holepunch_region_faces = None
+        log['holes'] = int(holes)
+        log['skips'] = [dict(component=c, reason=r) for c, r in skips]
 
     # -- curvature (block-boundary kernel) --------------------------------------------------------------------
     def _neighbor_tables(self):
@@ -294,7 +394,14 @@ class MembraneMesh(TriMesh):
         if not unobserved:
             self.update_geometry(vertex_normals=False)
         if plan.punch and done % self.delaunay_remesh_frequency == 0 and self.hole_puncher is not None:   # :1530-1532
-            self.hole_puncher(self, points, self.delaunay_eps)
+            if self.hole_puncher == 'device':
+                self._punch_iteration = done
+                try:
+                    self.punch_holes(points, self.delaunay_eps)
+                finally:
+                    self._punch_iteration = None
+            else:
+                self.hole_puncher(self, points, self.delaunay_eps)
             self._host_mesh_changed()
         if plan.remesh and done % self.remesh_frequency == 0:                                             # :1537-1549
             first = getattr(self, 'neck_first_iter', -1)
@@ -319,6 +426,7 @@ class MembraneMesh(TriMesh):
         if self._native is None:
             self._native = NativeContext(self._device)      # localizations stay in HBM across blocks
         self._host_mesh_changed()
+        self._holepunch_key = None          # (the localizations go to the hole-punch grid once per fit, at its first punch)
         self.cg = None
         done = 0
         self._in_fit = True
@@ -424,11 +532,14 @@ class ShrinkwrapMembrane(object):
         self.minimum_edge_length = 5.0
         self.smooth_curvature = True
         self.device = 0
+        self.hole_puncher = None                   # not a trait upstream: 'device' = punch_holes with the point queries on the GPU (include/nw_holepunch.h); None = punch_frequency does nothing
         self.remesher = 'device'                   # not a trait upstream (PYME always remeshes): 'device' = this package's remesher on the GPU (nw_remesh_device), 'builtin' = the same algorithm on the host (nwr_remesh), None holds the topology fixed
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise AttributeError('unknown parameter %s' % k)
             setattr(self, k, v)
+        if not (self.hole_puncher is None or self.hole_puncher == 'device' or (callable(self.hole_puncher) and not isinstance(self.hole_puncher, str))):
+            raise ValueError("hole_puncher must be None, 'device' or a callable(mesh, points, eps)")
 
     def execute(self, namespace):
         import time
@@ -440,7 +551,8 @@ class ShrinkwrapMembrane(object):
                             remesh_frequency=self.remesh_frequency, delaunay_remesh_frequency=self.punch_frequency,
                             delaunay_eps=self.min_hole_radius, neck_threshold_low=self.neck_threshold_low,
                             neck_threshold_high=self.neck_threshold_high, neck_first_iter=self.neck_first_iter,
-                            shrink_weight=self.shrink_weight, truncate_at=self.truncate_at, remesher=self.remesher)
+                            shrink_weight=self.shrink_weight, truncate_at=self.truncate_at, remesher=self.remesher,
+                            hole_puncher=self.hole_puncher)
         namespace[self.output] = mesh
         src = namespace[self.points]
         pts = np.ascontiguousarray(np.vstack([src['x'], src['y'], src['z']]).T)
