@@ -1,7 +1,7 @@
 """
 Builds the native pieces in-tree (no pip, no JIT cache):
   * ch_shrinkwrap_amd/libnanowrap_hip.so  -- the HIP kernels + C-ABI (hipcc, --offload-arch=gfx950): csrc/nanowrap.hip, nw_sort.hip, nw_remesh_dev.hip,
-                                            nw_holepunch.hip (include/nw_holepunch.h)
+                                            nw_holepunch.hip (include/nw_holepunch.h), nw_surgery.hip (include/nw_surgery.h)
   * ch_shrinkwrap_amd/libnw_remesh.so     -- the block-boundary remesher (host C++, g++; include/nw_remesh.h)
 The oracle (test infrastructure) is built by oracle/Makefile, see __graft_entry__.build().
 """
@@ -19,9 +19,12 @@ OBJ_REMESH = os.path.join(HERE, 'csrc', 'nw_remesh_dev.o')
 SRC_HOLEPUNCH = os.path.join(HERE, 'csrc', 'nw_holepunch.hip')  # the hole-punch point queries (include/nw_holepunch.h), its own translation unit
 OBJ_HOLEPUNCH = os.path.join(HERE, 'csrc', 'nw_holepunch.o')
 HDR_HOLEPUNCH = os.path.join(os.path.dirname(HERE), 'include', 'nw_holepunch.h')
+SRC_SURGERY = os.path.join(HERE, 'csrc', 'nw_surgery.hip')      # the neck / short-edge / inner-surface queries (include/nw_surgery.h), its own translation unit
+OBJ_SURGERY = os.path.join(HERE, 'csrc', 'nw_surgery.o')
+HDR_SURGERY = os.path.join(os.path.dirname(HERE), 'include', 'nw_surgery.h')
 import glob
 # every header of csrc/ is included by nanowrap.hip (directly or through nw_kernels.h): editing any of them must rebuild the library
-DEPS = [SRC, SRC_SORT, SRC_REMESH, SRC_HOLEPUNCH, HDR_HOLEPUNCH] + sorted(glob.glob(os.path.join(HERE, 'csrc', '*.h'))) + [os.path.join(os.path.dirname(HERE), 'include', 'nanowrap.h')]
+DEPS = [SRC, SRC_SORT, SRC_REMESH, SRC_HOLEPUNCH, HDR_HOLEPUNCH, SRC_SURGERY, HDR_SURGERY] + sorted(glob.glob(os.path.join(HERE, 'csrc', '*.h'))) + [os.path.join(os.path.dirname(HERE), 'include', 'nanowrap.h')]
 
 # -ffp-contract=off : the parity-critical float32 arithmetic must round products before adding, exactly like
 #                     the NumPy reference (explicit fma() is used where contraction is wanted);
@@ -56,9 +59,13 @@ def build_hip_library(force=False, verbose=False):
         # (-ffp-contract=off: the pairing kernel must round every product as the reference's C loop does -- its result is bit-identical)
         run([hipcc, '-O3', '--offload-arch=gfx950', '-fPIC', '-fvisibility=hidden', '-ffp-contract=off', '-Wall', '-Wno-unused-function',
              '-c', '-o', OBJ_HOLEPUNCH, SRC_HOLEPUNCH])
+    if force or not os.path.exists(OBJ_SURGERY) or os.path.getmtime(OBJ_SURGERY) < max(os.path.getmtime(SRC_SURGERY), os.path.getmtime(HDR_SURGERY)):
+        # (-ffp-contract=off: the half-edge lengths must round every product as TriMesh's do -- the short-edge selection is bit-identical)
+        run([hipcc, '-O3', '--offload-arch=gfx950', '-fPIC', '-fvisibility=hidden', '-ffp-contract=off', '-Wall', '-Wno-unused-function',
+             '-c', '-o', OBJ_SURGERY, SRC_SURGERY])
     run([hipcc] + [f for f in HIPCC_FLAGS if f != '-shared'] + ['-c', '-o', OBJ_MAIN, SRC])
     check_kernel_budgets(verbose=verbose)          # before the link: a kernel that spills or outgrows its occupancy never ships
-    run([hipcc, '--offload-arch=gfx950', '-fPIC', '-shared', '-o', LIB, OBJ_MAIN, OBJ_SORT, OBJ_REMESH, OBJ_HOLEPUNCH])
+    run([hipcc, '--offload-arch=gfx950', '-fPIC', '-shared', '-o', LIB, OBJ_MAIN, OBJ_SORT, OBJ_REMESH, OBJ_HOLEPUNCH, OBJ_SURGERY])
     return LIB
 
 
@@ -92,8 +99,24 @@ KERNEL_BUDGETS = {
     'k_hp_bbox':                      (32, 0),
     'k_hp_cand_geom':                 (32, 0),
     'k_hp_pair_final':                (16, 0),
+    # neck removal / short-edge cleanup / inner surfaces (csrc/nw_surgery.o): block-boundary queries, budgeted for zero scratch
+    'k_ws_init':                      (16, 0),
+    'k_ws_hook':                      (32, 0),
+    'k_ws_compress':                  (16, 0),
+    'k_ws_number':                    (16, 0),
+    'k_ws_scan_tiles':                (32, 1024),
+    'k_ws_scan_bsums':                (32, 1024),
+    'k_ws_scan_final':                (32, 1024),
+    'k_ws_stats':                     (64, 0),
+    'k_ws_bbox_init':                 (16, 0),
+    'k_ws_active':                    (16, 0),
+    'k_ws_winding':                   (176, 0),            # eight queries' float64 coordinates and fixed-point sums per thread (2 waves per SIMD)
+    'k_ws_lengths':                   (16, 0),
+    'k_ws_hist':                      (16, 2048),          # two 256-bin histograms
+    'k_ws_pick':                      (32, 0),
+    'k_ws_flag':                      (16, 0),
 }
-BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH]
+BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY]
 
 
 def kernel_resources(obj=None):

@@ -13,7 +13,10 @@ PYME's part is the topology surgery at block boundaries -- `remesh`, the deletio
 `punch_holes`, `remove_extra_short_edges`: they are hooks (`remesher`, `neck_remover`, `hole_puncher`, `edge_cleaner`).
 For `remesh` this package ships its own implementation of the published algorithm (`remesher='builtin'`, remesh.py /
 csrc/remesh.cpp); when no hook is installed the topology is held fixed and that is logged once.
-`punch_holes` is defined upstream itself (:877-1199) and is mirrored here (`hole_puncher='device'`: holepunch.py, csrc/nw_holepunch.hip).  The numerical path of every block is the HIP library; there is no CPU fallback.
+`punch_holes` is defined upstream itself (:877-1199) and is mirrored here (`hole_puncher='device'`: holepunch.py, csrc/nw_holepunch.hip).
+`remove_necks` / `remove_extra_short_edges` (:1201-1239) run upstream's sequence unsafe_remove_vertices -> repair -> remesh -> remove_inner_surfaces
+with `neck_remover='device'` / `edge_cleaner='device'`: those four are this package's own (surgery.py, csrc/nw_surgery.hip), and the neck
+selection passes a guard that keeps noise from being cut.  The numerical path of every block is the HIP library; there is no CPU fallback.
 """
 import math
 import os
@@ -58,15 +61,22 @@ class MembraneMesh(TriMesh):
         self.cg = None
         # block-boundary topology hooks (PYME's job in the reference; see module docstring)
         self.remesher = None          # None | 'builtin' (host C++) | 'device' (GPU) | callable(mesh, n, target_edge_length, l, n_relax)
-        self.neck_remover = None      # callable(mesh, vertex_ids): delete + repair + remesh (PYME's part of remove_necks)
+        self.neck_remover = None      # None (selection only) | 'device' (remove_necks: guarded cut, repair, remesh) | callable(mesh, vertex_ids)
         self.hole_puncher = None      # None (no punching) | 'device' (punch_holes: point queries on the GPU) | callable(mesh, points, eps)
-        self.edge_cleaner = None      # callable(mesh)  (remove_extra_short_edges)
+        self.edge_cleaner = None      # None | 'device' (remove_extra_short_edges at every remesh) | callable(mesh)
+        # neck guard (remove_necks with neck_remover='device'): see _remove_necks_device
+        self.neck_guard = True
+        self.neck_max_regions = 32
+        self.neck_min_piece_faces = 200
+        self.min_component_faces = 32  # repair(): closed components with fewer faces are dropped as dust
         self._device = device
         self._native = None
         self._warned_fixed_topology = False
         self.block_log = []
         self.neck_log = []
         self.punch_log = []
+        self.edge_log = []
+        self._surgery = None          # SurgeryContext (csrc/nw_surgery.hip): labelling, component statistics, winding numbers, short edges
         self._holepunch = None        # HolePunchContext of the fit (the localizations' cell grid lives on the device beside _native's)
         self._holepunch_key = None
         self._initialize_curvature_vectors()
@@ -83,6 +93,26 @@ class MembraneMesh(TriMesh):
         if not (value is None or value == 'device' or (callable(value) and not isinstance(value, str))):
             raise ValueError("hole_puncher must be None, 'device' or a callable(mesh, points, eps)")
         self.__dict__['_hole_puncher'] = value
+
+    @property
+    def neck_remover(self):
+        return self.__dict__.get('_neck_remover')
+
+    @neck_remover.setter
+    def neck_remover(self, value):
+        if not (value is None or value == 'device' or (callable(value) and not isinstance(value, str))):
+            raise ValueError("neck_remover must be None, 'device' or a callable(mesh, vertex_ids)")
+        self.__dict__['_neck_remover'] = value
+
+    @property
+    def edge_cleaner(self):
+        return self.__dict__.get('_edge_cleaner')
+
+    @edge_cleaner.setter
+    def edge_cleaner(self, value):
+        if not (value is None or value == 'device' or (callable(value) and not isinstance(value, str))):
+            raise ValueError("edge_cleaner must be None, 'device' or a callable(mesh)")
+        self.__dict__['_edge_cleaner'] = value
 
     def _topology_changed(self, vertices, faces, all_referenced=False, mean_edge=None):
         """Rebuild the half-edge tables for a new (vertices, faces) pair; the optimiser of the old topology is dropped."""
@@ -129,14 +159,153 @@ class MembraneMesh(TriMesh):
         return np.flatnonzero((K < neck_curvature_threshold_low) | (K > neck_curvature_threshold_high))
 
     def remove_necks(self, neck_curvature_threshold_low=-1e-4, neck_curvature_threshold_high=1e-2):
-        """_membrane_mesh.pyx:1201-1219.  Deleting the selected vertices, repairing, remeshing and dropping inner
-        surfaces are PYME TriangleMesh operations; they run through the `neck_remover` hook.  Returns the selection."""
+        """_membrane_mesh.pyx:1201-1219.  `neck_remover`: None = selection only; 'device' = upstream's sequence behind the neck guard
+        (_remove_necks_device, one `neck_log` entry per call); a callable(mesh, vertex_ids) does the rest itself.  Returns the selection."""
         verts = self.neck_vertices(neck_curvature_threshold_low, neck_curvature_threshold_high)
-        if len(verts) > 0 and self.neck_remover is not None:
+        if self.neck_remover == 'device':
+            self._remove_necks_device(verts)
+        elif len(verts) > 0 and self.neck_remover is not None:
             self.neck_remover(self, verts)
             self.cg = None
             self._host_mesh_changed()
         return verts
+
+    # -- topology surgery (upstream's remove_necks / remove_extra_short_edges; PYME's primitives, defined in surgery.py) -----------
+    def _surgery_context(self):
+        from .surgery import SurgeryContext
+        if self._surgery is None:
+            self._surgery = SurgeryContext(self._device)
+        return self._surgery
+
+    def _label_faces(self, faces, twin, mask=None):
+        return self._surgery_context().label_faces(faces, twin, mask)
+
+    def _surgery_arrays(self):
+        """(positions (V,3) float32, faces (F,3) int32, twin (3F,) int32) of the mesh as it stands (copies: the surgery replaces it)"""
+        pos = np.array(self.vertices, np.float32, order='C')
+        faces = np.ascontiguousarray(self.faces, np.int32)
+        try:
+            from .remesh import halfedge_twins
+            twin = halfedge_twins(faces, pos.shape[0])
+        except (RuntimeError, ValueError):
+            from .surgery import twins
+            twin = twins(faces, pos.shape[0])
+        return pos, faces, twin
+
+    def _surgery_update(self, vertices, faces, all_referenced=False):
+        """Rebuild for the new topology (as _holepunch_update_topology does): the optimiser of the old one and the device copy are stale."""
+        self._topology_changed(vertices, faces, all_referenced=all_referenced)
+        self.cg = None
+        self._host_mesh_changed()
+
+    def unsafe_remove_vertices(self, vertex_ids):
+        """Delete the vertices and every face with a corner among them; may leave borders (twin -1) and unreferenced vertex slots --
+        repair() closes the one and drops the other.  Returns the number of faces removed."""
+        from .surgery import excise
+        pos = np.array(self.vertices, np.float32, order='C')
+        faces = np.asarray(self.faces)
+        keep = excise(faces, vertex_ids, pos.shape[0])
+        if keep.all():
+            return 0
+        self._surgery_update(pos, np.ascontiguousarray(faces[keep], np.int32))
+        return int((~keep).sum())
+
+    def repair(self):
+        """Make the mesh a closed oriented 2-manifold again (surgery.repair: bow-tie vertices and three-border faces go, every border loop
+        is capped with new vertices, closed components under `min_component_faces` faces are dropped and logged).  Returns its info."""
+        from .surgery import repair
+        pos = np.array(self.vertices, np.float32, order='C')
+        v, f, info = repair(pos, self.faces, self._label_faces, self.min_component_faces)
+        for c, n in info['dust']:
+            print('MembraneMesh.repair: dropped a closed component of %d faces (< min_component_faces = %d)' % (n, self.min_component_faces))
+        self._surgery_update(v, f, all_referenced=True)
+        return info
+
+    def remove_inner_surfaces(self):
+        """Drop every component that is an inverted shell (signed volume <= 0) or lies inside another kept, positively oriented one (more
+        than half of up to 16 sample vertices at winding number >= 0.5; surgery.inner_components).  PYME's definition is not in the
+        reference: this is the package's own.  Returns [(component, reason)]; every removal is logged."""
+        from .surgery import sample_vertices, inner_components
+        pos, faces, twin = self._surgery_arrays()
+        ctx = self._surgery_context()
+        lab, n = ctx.label_faces(faces, twin)
+        if n == 0:
+            return []
+        st = ctx.component_stats(pos, faces, twin, lab, n)
+        samples = sample_vertices(faces, lab, n)
+        removed = inner_components(st['volume'], samples, lambda qv, qc: ctx.winding(pos, faces, lab, n, pos[qv], qc))
+        if removed:
+            for c, reason in removed:
+                print('MembraneMesh.remove_inner_surfaces: component %d of %d (%d faces) removed: %s' % (c, n, st['faces'][c], reason))
+            gone = np.zeros(n, bool)
+            gone[[c for c, _ in removed]] = True
+            f = faces[~gone[lab]]
+            used = np.zeros(pos.shape[0], bool)
+            used[f.ravel()] = True
+            remap = np.cumsum(used) - 1
+            self._surgery_update(pos[used], np.ascontiguousarray(remap[f], np.int32), all_referenced=True)
+        return removed
+
+    def _surgery_sequence(self, vertex_ids):
+        """upstream's unsafe_remove_vertices -> repair -> remesh(n_relax=0) -> remove_inner_surfaces (:1215-1219, :1233-1237)"""
+        self.unsafe_remove_vertices(vertex_ids)
+        info = self.repair()
+        self.remesh(n_relax=0)
+        return info, self.remove_inner_surfaces()
+
+    def remove_extra_short_edges(self, threshold=0.05):
+        """:1221-1237: every vertex at the head of a half-edge shorter than threshold * median (nws_short_edge_vertices: the same float32
+        lengths as the half-edge records', numpy's median) goes, then repair, remesh, remove_inner_surfaces.  Nothing happens when no
+        vertex is flagged.  Every call appends to `edge_log`; returns the flagged vertices."""
+        pos, faces, _ = self._surgery_arrays()
+        flags, median = self._surgery_context().short_edge_vertices(pos, faces, threshold)
+        verts = np.flatnonzero(flags)
+        rec = dict(iteration=getattr(self, '_edge_iteration', None), median=float(median), threshold=float(threshold), vertices=int(verts.size))
+        self.edge_log.append(rec)
+        if verts.size:
+            info, removed = self._surgery_sequence(verts)
+            rec.update(loops_capped=info['loops'], removed_inner=removed, faces_after=int(self.faces.shape[0]))
+        return verts
+
+    def _remove_necks_device(self, verts):
+        """remove_necks with neck_remover='device'.  With `neck_guard` (default) only real necks are cut:
+          1. regions = edge-connected components of the faces with a candidate corner (exactly what unsafe_remove_vertices would delete);
+          2. a region that is a disk (Euler characteristic 1, one border loop) is a bump: cutting and capping it changes no topology;
+          3. the other regions, in order of their smallest face id, at most `neck_max_regions`: a region is accepted if every piece of
+             the mesh bordering it (the mesh without it and without the regions accepted so far) keeps `neck_min_piece_faces` faces;
+          4. the accepted regions' candidates go through unsafe_remove_vertices -> repair -> remesh(n_relax=0) -> remove_inner_surfaces.
+        Without the guard every candidate goes, as upstream.  When nothing is cut the mesh is not touched."""
+        from .surgery import guard_regions
+        rec = dict(iteration=getattr(self, '_neck_iteration', None), candidates=int(len(verts)), regions=0, disks=0, examined=0, cut=0,
+                   skips=[], loops_capped=0, components_before=None, components_after=None, removed_inner=[])
+        self.neck_log.append(rec)
+        if len(verts) == 0:
+            return rec
+        pos, faces, twin = self._surgery_arrays()
+        cand = np.zeros(pos.shape[0], bool)
+        cand[np.asarray(verts)] = True
+        region_faces = cand[faces].any(1)
+        lab, n = self._label_faces(faces, twin, region_faces.astype(np.uint8))
+        rec['regions'] = int(n)
+        if self.neck_guard:
+            accepted, skips, info = guard_regions(faces, twin, lab, n, self._label_faces, self.neck_max_regions, self.neck_min_piece_faces)
+            rec.update(disks=info['disks'], examined=info['examined'], cut=len(accepted), skips=skips)
+            if not accepted:
+                return rec
+            ok = np.zeros(n, bool)
+            ok[accepted] = True
+            cut = np.zeros(pos.shape[0], bool)
+            cut[faces[ok[np.maximum(lab, 0)] & (lab >= 0)].ravel()] = True
+            cut_verts = np.flatnonzero(cut & cand)
+        else:
+            rec['cut'] = int(n)
+            cut_verts = np.asarray(verts)
+        rec['components_before'] = int(self._label_faces(faces, twin)[1])
+        info, removed = self._surgery_sequence(cut_verts)
+        rec.update(loops_capped=info['loops'], removed_inner=removed)
+        _, f2, t2 = self._surgery_arrays()
+        rec['components_after'] = int(self._label_faces(f2, t2)[1]) if f2.shape[0] else 0
+        return rec
 
     # -- hole punching (_membrane_mesh.pyx:877-1199): steps 1-3 on the GPU, 4-6 on the host over the candidates ------------------
     def _holepunch_context(self, points=None):
@@ -406,11 +575,23 @@ class MembraneMesh(TriMesh):
         if plan.remesh and done % self.remesh_frequency == 0:                                             # :1537-1549
             first = getattr(self, 'neck_first_iter', -1)
             if first > 0 and done > first:                                                                # :1538-1540
-                verts = self.remove_necks(getattr(self, 'neck_threshold_low', -1e-4), getattr(self, 'neck_threshold_high', 1e-2))
-                self.neck_log.append(dict(iteration=done, candidates=int(len(verts))))
+                self._neck_iteration = done
+                try:
+                    verts = self.remove_necks(getattr(self, 'neck_threshold_low', -1e-4), getattr(self, 'neck_threshold_high', 1e-2))
+                finally:
+                    self._neck_iteration = None
+                if self.neck_remover != 'device':                  # (the device path logs its own, richer entry)
+                    self.neck_log.append(dict(iteration=done, candidates=int(len(verts))))
                 self._host_mesh_changed()
-            if self.edge_cleaner is not None:
-                self.edge_cleaner(self)
+            if self.edge_cleaner is not None:                                                             # :1541
+                if self.edge_cleaner == 'device':
+                    self._edge_iteration = done
+                    try:
+                        self.remove_extra_short_edges()
+                    finally:
+                        self._edge_iteration = None
+                else:
+                    self.edge_cleaner(self)
                 self._host_mesh_changed()
             target = plan.target_length(done)
             if self.remesh(5, target, 0.5, n_relax=0):
@@ -533,6 +714,8 @@ class ShrinkwrapMembrane(object):
         self.smooth_curvature = True
         self.device = 0
         self.hole_puncher = None                   # not a trait upstream: 'device' = punch_holes with the point queries on the GPU (include/nw_holepunch.h); None = punch_frequency does nothing
+        self.neck_remover = None                   # not a trait upstream: 'device' = remove_necks cuts guarded necks (include/nw_surgery.h); None = the neck traits only select
+        self.edge_cleaner = None                   # not a trait upstream: 'device' = remove_extra_short_edges at every remesh; None = not run
         self.remesher = 'device'                   # not a trait upstream (PYME always remeshes): 'device' = this package's remesher on the GPU (nw_remesh_device), 'builtin' = the same algorithm on the host (nwr_remesh), None holds the topology fixed
         for k, v in kw.items():
             if not hasattr(self, k):
@@ -540,6 +723,10 @@ class ShrinkwrapMembrane(object):
             setattr(self, k, v)
         if not (self.hole_puncher is None or self.hole_puncher == 'device' or (callable(self.hole_puncher) and not isinstance(self.hole_puncher, str))):
             raise ValueError("hole_puncher must be None, 'device' or a callable(mesh, points, eps)")
+        for name in ('neck_remover', 'edge_cleaner'):
+            v = getattr(self, name)
+            if not (v is None or v == 'device' or (callable(v) and not isinstance(v, str))):
+                raise ValueError("%s must be None, 'device' or a callable" % name)
 
     def execute(self, namespace):
         import time
@@ -552,7 +739,7 @@ class ShrinkwrapMembrane(object):
                             delaunay_eps=self.min_hole_radius, neck_threshold_low=self.neck_threshold_low,
                             neck_threshold_high=self.neck_threshold_high, neck_first_iter=self.neck_first_iter,
                             shrink_weight=self.shrink_weight, truncate_at=self.truncate_at, remesher=self.remesher,
-                            hole_puncher=self.hole_puncher)
+                            hole_puncher=self.hole_puncher, neck_remover=self.neck_remover, edge_cleaner=self.edge_cleaner)
         namespace[self.output] = mesh
         src = namespace[self.points]
         pts = np.ascontiguousarray(np.vstack([src['x'], src['y'], src['z']]).T)
