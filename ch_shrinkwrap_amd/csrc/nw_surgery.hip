@@ -211,27 +211,40 @@ __device__ __forceinline__ int ws_wave_label(int lab)
 
 struct ws_acc {
     u64 *count, *area, *vol, *border;      // C each (fixed point for area / vol, two's complement in u64)
+    u64 *nrm;                              // 3C: sum of (p1 - p0) x (p2 - p0), fixed point (the volume's change of origin)
     int *bbox;                             // 6C ordered ints
 };
 
+// the frame of one call: terms are taken relative to o (the float32 centre of pos's bounding box), so that their fixed-point scales follow
+// the mesh's extent and not its distance from the origin
+struct ws_frame {
+    double o[3];
+    double s_area, s_vol, s_nrm;
+};
+
 __global__ __launch_bounds__(NWS_BLOCK) void k_ws_stats(const float *__restrict__ pos, const int *__restrict__ faces, const int *__restrict__ twin,
-                                                        const int *__restrict__ label, int nf, double s_area, double s_vol, ws_acc acc)
+                                                        const int *__restrict__ label, int nf, ws_frame fr, ws_acc acc)
 {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     const int lab = f < nf ? label[f] : -1;
-    i64 ca = 0, cv = 0, cb = 0, cc = 0;
+    i64 ca = 0, cv = 0, cb = 0, cc = 0, cn[3] = {0, 0, 0};
     int lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {INT_MIN, INT_MIN, INT_MIN};
     if (lab >= 0) {
         const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
-        const double x0 = pos[3 * i0], y0 = pos[3 * i0 + 1], z0 = pos[3 * i0 + 2];
-        const double x1 = pos[3 * i1], y1 = pos[3 * i1 + 1], z1 = pos[3 * i1 + 2];
-        const double x2 = pos[3 * i2], y2 = pos[3 * i2 + 1], z2 = pos[3 * i2 + 2];
+        // (a float32 minus the float32 centre is exact in float64 unless the two are 2^29 apart)
+        const double x0 = (double)pos[3 * i0] - fr.o[0], y0 = (double)pos[3 * i0 + 1] - fr.o[1], z0 = (double)pos[3 * i0 + 2] - fr.o[2];
+        const double x1 = (double)pos[3 * i1] - fr.o[0], y1 = (double)pos[3 * i1 + 1] - fr.o[1], z1 = (double)pos[3 * i1 + 2] - fr.o[2];
+        const double x2 = (double)pos[3 * i2] - fr.o[0], y2 = (double)pos[3 * i2 + 1] - fr.o[1], z2 = (double)pos[3 * i2 + 2] - fr.o[2];
         const double ax = x1 - x0, ay = y1 - y0, az = z1 - z0, bx = x2 - x0, by = y2 - y0, bz = z2 - z0;
         const double cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
         const double area = 0.5 * sqrt(cx * cx + cy * cy + cz * cz);
         const double vol = (x0 * (y1 * z2 - z1 * y2) + y0 * (z1 * x2 - x1 * z2) + z0 * (x1 * y2 - y1 * x2)) / 6.0;
-        ca = llrint(area * s_area);
-        cv = llrint(vol * s_vol);
+        // p0 . (p1 x p2) = q0 . (q1 x q2) + o . ((q1 - q0) x (q2 - q0)) with q = p - o: the second part is summed apart, added on the host
+        ca = llrint(area * fr.s_area);
+        cv = llrint(vol * fr.s_vol);
+        cn[0] = llrint(cx * fr.s_nrm);
+        cn[1] = llrint(cy * fr.s_nrm);
+        cn[2] = llrint(cz * fr.s_nrm);
         cc = 1;
         for (int k = 0; k < 3; ++k) {
             const int t = twin[3 * f + k];
@@ -247,6 +260,7 @@ __global__ __launch_bounds__(NWS_BLOCK) void k_ws_stats(const float *__restrict_
     if (wl == -1) return;
     if (wl >= 0) {
         ca = ws_wave_sum(ca); cv = ws_wave_sum(cv); cb = ws_wave_sum(cb); cc = ws_wave_sum(cc);
+        for (int d = 0; d < 3; ++d) cn[d] = ws_wave_sum(cn[d]);
         for (int d = 0; d < 3; ++d) { lo[d] = ws_wave_min(lo[d]); hi[d] = ws_wave_max(hi[d]); }
         if ((threadIdx.x & 63) != 0) return;
         c = wl;
@@ -256,6 +270,7 @@ __global__ __launch_bounds__(NWS_BLOCK) void k_ws_stats(const float *__restrict_
     atomicAdd(&acc.area[c], (u64)ca);
     atomicAdd(&acc.vol[c], (u64)cv);
     atomicAdd(&acc.border[c], (u64)cb);
+    for (int d = 0; d < 3; ++d) atomicAdd(&acc.nrm[3 * c + d], (u64)cn[d]);
     for (int d = 0; d < 3; ++d) { atomicMin(&acc.bbox[6 * c + d], lo[d]); atomicMax(&acc.bbox[6 * c + 3 + d], hi[d]); }
 }
 
@@ -546,23 +561,40 @@ double fixed_scale(double n_terms, double bound)
     return std::ldexp(1.0, (int)std::floor(62.0 - std::log2(bound)));
 }
 
+// the frame of pos: o = the centre of its bounding box rounded to float32, M = max |p - o|, and the fixed-point scales that follow from M
+ws_frame make_frame(const float *pos, int64_t nv, int nf)
+{
+    float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+    for (int64_t i = 0; i < nv; ++i)
+        for (int d = 0; d < 3; ++d) { lo[d] = std::min(lo[d], pos[3 * i + d]); hi[d] = std::max(hi[d], pos[3 * i + d]); }
+    ws_frame fr;
+    double M = 1e-30;
+    for (int d = 0; d < 3; ++d) {
+        fr.o[d] = nv > 0 ? (double)(float)(0.5 * ((double)lo[d] + (double)hi[d])) : 0.0;
+        if (nv > 0) M = std::max(M, std::max((double)hi[d] - fr.o[d], fr.o[d] - (double)lo[d]));
+    }
+    fr.s_area = fixed_scale(nf, 6.0 * M * M);
+    fr.s_vol = fixed_scale(nf, M * M * M);
+    fr.s_nrm = fixed_scale(nf, 12.0 * M * M);
+    return fr;
+}
+
 float dec_ord(int v) { const int i = v >= 0 ? v : v ^ 0x7fffffff; float f; std::memcpy(&f, &i, 4); return f; }
 
-// the accumulators of k_ws_stats into the ctx's buffers c (u64: count, area, volume, border; C each) and d (bbox, 6C ordered ints); pos,
-// faces, twin and label are on the device already
-int run_stats(nws_ctx *ctx, int nf, int nc, float max_abs)
+// the accumulators of k_ws_stats into the ctx's buffers c (u64: count, area, volume, border, C each, then the 3C normal sums) and d (bbox,
+// 6C ordered ints); pos, faces, twin and label are on the device already
+int run_stats(nws_ctx *ctx, int nf, int nc, const ws_frame &fr)
 {
-    NWS_HIP(ctx->c.ensure(sizeof(u64) * 4 * (size_t)nc));
+    NWS_HIP(ctx->c.ensure(sizeof(u64) * 7 * (size_t)nc));
     NWS_HIP(ctx->d.ensure(sizeof(int) * 6 * (size_t)nc));
-    NWS_HIP(hipMemsetAsync(ctx->c.p, 0, sizeof(u64) * 4 * (size_t)nc, ctx->stream));
+    NWS_HIP(hipMemsetAsync(ctx->c.p, 0, sizeof(u64) * 7 * (size_t)nc, ctx->stream));
     hipLaunchKernelGGL(k_ws_bbox_init, dim3(nblk(6 * (int64_t)nc)), dim3(NWS_BLOCK), 0, ctx->stream, ctx->d.as<int>(), 6 * nc);
-    const double M = std::max((double)max_abs, 1e-30);
     ws_acc acc;
     u64 *base = ctx->c.as<u64>();
-    acc.count = base; acc.area = base + nc; acc.vol = base + 2 * (size_t)nc; acc.border = base + 3 * (size_t)nc;
+    acc.count = base; acc.area = base + nc; acc.vol = base + 2 * (size_t)nc; acc.border = base + 3 * (size_t)nc; acc.nrm = base + 4 * (size_t)nc;
     acc.bbox = ctx->d.as<int>();
     hipLaunchKernelGGL(k_ws_stats, dim3(nblk(nf)), dim3(NWS_BLOCK), 0, ctx->stream, ctx->pos.as<float>(), ctx->faces.as<int>(), ctx->twin.as<int>(),
-                       ctx->label.as<int>(), nf, fixed_scale(nf, 6.0 * M * M), fixed_scale(nf, M * M * M), acc);
+                       ctx->label.as<int>(), nf, fr, acc);
     NWS_HIP(hipGetLastError());
     return NWS_OK;
 }
@@ -638,9 +670,8 @@ NWS_EXPORT int nws_component_stats(nws_ctx *ctx, const float *pos, int64_t n_ver
                                    int64_t *n_border)
 {
     if (n_components < 0 || n_components > (1 << 28)) return NWS_ERR_BADARG;
-    float max_abs = 0.0f;
     NWS_TRY(check_faces(faces, n_faces, n_vertices));
-    NWS_TRY(check_pos(pos, n_vertices, &max_abs));
+    NWS_TRY(check_pos(pos, n_vertices, nullptr));
     NWS_TRY(check_twin(twin, n_faces));
     NWS_TRY(check_label(label, n_faces, n_components));
     if (!ctx) return NWS_ERR_BADARG;
@@ -651,18 +682,22 @@ NWS_EXPORT int nws_component_stats(nws_ctx *ctx, const float *pos, int64_t n_ver
     NWS_TRY(upload(ctx, ctx->faces, faces, 3 * n_faces));
     NWS_TRY(upload(ctx, ctx->twin, twin, 3 * n_faces));
     NWS_TRY(upload(ctx, ctx->label, label, n_faces));
-    NWS_TRY(run_stats(ctx, nf, nc, max_abs));
-    std::vector<u64> acc(4 * (size_t)nc);
+    const ws_frame fr = make_frame(pos, n_vertices, nf);
+    NWS_TRY(run_stats(ctx, nf, nc, fr));
+    std::vector<u64> acc(7 * (size_t)nc);
     std::vector<int> bb(6 * (size_t)nc);
     NWS_HIP(hipMemcpyAsync(acc.data(), ctx->c.p, sizeof(u64) * acc.size(), hipMemcpyDeviceToHost, ctx->stream));
     NWS_HIP(hipMemcpyAsync(bb.data(), ctx->d.p, sizeof(int) * bb.size(), hipMemcpyDeviceToHost, ctx->stream));
     NWS_HIP(hipStreamSynchronize(ctx->stream));
-    const double M = std::max((double)max_abs, 1e-30);
-    const double sa = fixed_scale(nf, 6.0 * M * M), sv = fixed_scale(nf, M * M * M);
     for (int c = 0; c < nc; ++c) {
         if (face_count) face_count[c] = (int64_t)acc[c];
-        if (area) area[c] = (double)(int64_t)acc[nc + c] / sa;
-        if (volume) volume[c] = (double)(int64_t)acc[2 * (size_t)nc + c] / sv;
+        if (area) area[c] = (double)(int64_t)acc[nc + c] / fr.s_area;
+        if (volume) {
+            // about o, plus o . (sum of the face normals) / 6: the volume about the origin (the second part is ~0 for a closed component)
+            const u64 *n = &acc[4 * (size_t)nc + 3 * (size_t)c];
+            const double shift = (fr.o[0] * (double)(int64_t)n[0] + fr.o[1] * (double)(int64_t)n[1] + fr.o[2] * (double)(int64_t)n[2]) / fr.s_nrm;
+            volume[c] = (double)(int64_t)acc[2 * (size_t)nc + c] / fr.s_vol + shift / 6.0;
+        }
         if (n_border) n_border[c] = (int64_t)acc[3 * (size_t)nc + c];
         if (bbox)
             for (int d = 0; d < 6; ++d) {
@@ -679,9 +714,8 @@ NWS_EXPORT int nws_winding(nws_ctx *ctx, const float *pos, int64_t n_vertices, c
     if (!queries || !w_out || n_queries < 0 || n_queries > (1 << 24) || n_components < 0 || n_components > (1 << 24) ||
         n_queries * (int64_t)n_components > (1ll << 28))
         return NWS_ERR_BADARG;
-    float max_abs = 0.0f;
     NWS_TRY(check_faces(faces, n_faces, n_vertices));
-    NWS_TRY(check_pos(pos, n_vertices, &max_abs));
+    NWS_TRY(check_pos(pos, n_vertices, nullptr));
     NWS_TRY(check_label(label, n_faces, n_components));
     for (int64_t i = 0; i < 3 * n_queries; ++i)
         if (!std::isfinite(queries[i])) return NWS_ERR_BADARG;
@@ -705,7 +739,7 @@ NWS_EXPORT int nws_winding(nws_ctx *ctx, const float *pos, int64_t n_vertices, c
     // the boxes: k_ws_stats over a twin table of -1 (the border counts it also makes are not read)
     NWS_HIP(ctx->twin.ensure(sizeof(int) * 3 * (size_t)nf));
     NWS_HIP(hipMemsetAsync(ctx->twin.p, 0xff, sizeof(int) * 3 * (size_t)nf, ctx->stream));
-    NWS_TRY(run_stats(ctx, nf, nc, max_abs));
+    NWS_TRY(run_stats(ctx, nf, nc, make_frame(pos, n_vertices, nf)));
     NWS_HIP(ctx->e.ensure((size_t)nw));
     NWS_HIP(ctx->f.ensure(sizeof(u64) * (size_t)nw));
     NWS_HIP(hipMemsetAsync(ctx->f.p, 0, sizeof(u64) * (size_t)nw, ctx->stream));

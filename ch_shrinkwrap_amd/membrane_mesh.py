@@ -424,12 +424,18 @@ class MembraneMesh(TriMesh):
         M = self._position_records().shape[0]
         host_tables = os.environ.get('NW_HOST_TABLES', '0') == '1'
         key = getattr(nat, 'mesh_key', None)
-        if skip_prob == 0 and not host_tables and key is not None and key[0] == id(self) and key[1] == M and key[2] == int(self.faces.shape[0]):
+        resident = getattr(self, '_in_fit', False) and key is not None and key[0] == id(self) and key[1] == M and key[2] == int(self.faces.shape[0])
+        if skip_prob == 0 and not host_tables and resident:
             # the block that has just ended left THIS mesh on the device -- positions of its last iteration, normals refreshed there
             # (_block_boundary): nothing is uploaded, and the kernel's two tables are built on the device as well (nw_curvature with NULL
-            # tables, round 5) -- the block boundary's neck selection runs without a host table builder
+            # tables, round 5) -- the block boundary's neck selection runs without a host table builder.  Only inside a fit: afterwards the
+            # caller may have edited the positions, and the device copy is stale
             nxt, area = None, None
         else:
+            # (the host's 1-ring table has NEIGHBORSIZE slots and the kernel walks at most that many: a vertex with more outgoing half-edges
+            # would be computed on a truncated ring)
+            if self.faces.shape[0] and np.bincount(np.asarray(self.faces).ravel(), minlength=M).max() > self._vertices['neighbors'].shape[1]:
+                raise ValueError('curvature_grad_c: a vertex has more than %d neighbours (the 1-ring table is that wide)' % self._vertices['neighbors'].shape[1])
             pos = np.ascontiguousarray(self._vertices['position'], 'f4')
             nrm = np.ascontiguousarray(self.vertex_normals, 'f4')
             nbr = self.neighbor_vertex_table()
@@ -615,6 +621,8 @@ class MembraneMesh(TriMesh):
             return self._run_blocks(points, lams, s, weights, plan)
         finally:
             self._in_fit = False
+            # (the device copy mirrors the mesh only until the caller touches it: the next curvature read or remesh starts from the host)
+            self._host_mesh_changed()
 
     def _run_blocks(self, points, lams, s, weights, plan):
         done = 0

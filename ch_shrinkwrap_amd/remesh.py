@@ -224,11 +224,11 @@ def builtin_remesher(mesh, n=5, target_edge_length=-1, l=0.5, n_relax=10, _remes
     valid = mesh.valid_vertex_mask() if hasattr(mesh, 'valid_vertex_mask') else mesh._vertices['halfedge'] != -1
     pos = mesh.vertices if hasattr(mesh, 'valid_vertex_mask') else mesh._vertices['position']
     # (the block that has just ended returned the same positions as one contiguous array; while nothing has touched the host mesh since --
-    # the driver's mesh_key says so -- that array saves gathering 12-byte rows out of 120-byte records)
+    # the driver's mesh_key says so, and only inside a fit -- that array saves gathering 12-byte rows out of 120-byte records)
     cg, nat = getattr(mesh, 'cg', None), getattr(mesh, '_native', None)
     key = getattr(nat, 'mesh_key', None)
     fs = getattr(cg, 'fs', None)
-    if key is not None and key[0] == id(mesh) and isinstance(fs, np.ndarray) and fs.dtype == np.float32 and fs.shape == pos.shape and fs.flags.c_contiguous:
+    if getattr(mesh, '_in_fit', False) and key is not None and key[0] == id(mesh) and isinstance(fs, np.ndarray) and fs.dtype == np.float32 and fs.shape == pos.shape and fs.flags.c_contiguous:
         pos = fs
     if valid.all():                                   # (the usual case: no spare or deleted vertex slots -- nothing to renumber)
         v, f = pos, mesh.faces

@@ -51,9 +51,12 @@ int nws_label_faces(nws_ctx *ctx, const int32_t *faces, const int32_t *twin, con
 /* Per component c of `label` (values -1 or 0..n_components-1): face_count[c], area[c] (sum of 0.5 |(p1-p0) x (p2-p0)|), volume[c]
  * (sum of p0 . (p1 x p2) / 6: positive for a closed surface whose faces wind counter-clockwise seen from outside), bbox[6c..6c+5]
  * (min xyz, max xyz of its corners; FLT_MAX / -FLT_MAX for an empty component) and n_border[c] (its half-edges whose twin is -1 or a face
- * of another label).  Terms in float64, summed in 64-bit fixed point: identical bytes on every run.  The resolution of area and volume
- * is 2^-k with 2^k = 2^62 / (n_faces * bound), bound = 6 M^2 for area and M^3 for volume, M = the largest |coordinate| of pos.
- * Any output may be NULL. */
+ * of another label).  Terms in float64, summed in 64-bit fixed point: identical bytes on every run.  Terms are taken relative to o, the
+ * centre of pos's bounding box rounded to float32: volume[c] = sum of q0 . (q1 x q2) / 6 with q = p - o, plus o . (sum of (q1 - q0) x
+ * (q2 - q0)) / 6 (which vanishes for a closed component), so that the resolution follows the mesh's extent, not its distance from the
+ * origin.  The resolution of a term is 2^-k with 2^k = 2^62 / (n_faces * bound), bound = 6 M^2 for area, M^3 for the volume about o and
+ * 12 M^2 for the normal sums, M = max |p - o| over pos: a component of n_c faces is within n_c 2^-k / 2 of the sum of its float64 terms
+ * (for the volume, plus |o|_1 n_c 2^-k / 12 from the normal sums).  Any output may be NULL. */
 int nws_component_stats(nws_ctx *ctx, const float *pos, int64_t n_vertices, const int32_t *faces, const int32_t *twin, const int32_t *label,
                         int64_t n_faces, int32_t n_components, int64_t *face_count, double *area, double *volume, float *bbox,
                         int64_t *n_border);

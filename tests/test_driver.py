@@ -411,3 +411,41 @@ def test_geometry_computed_on_first_use_equals_the_eager_one(recorder):
     ref = TriMesh(m.vertices.copy(), m.faces)
     assert abs(m.block_log[-1]['mean_length'] - float(ref._mean_edge_length)) < 1e-5 * float(ref._mean_edge_length)
     assert np.array_equal(m.face_normals, ref.face_normals) and m.area() == ref.area()
+
+
+def test_device_resident_shortcuts_are_not_taken_after_a_fit(recorder):
+    """The block loop's shortcuts -- the remesher reading the optimiser's `cg.fs`, the curvature kernel reading the device's positions -- are
+    valid only while a fit is running: a caller who edits `mesh.vertices` afterwards must have the edit seen."""
+    from ch_shrinkwrap_amd.remesh import builtin_remesher
+    m = _mesh(kc=1.0, max_iter=4, remesh_frequency=0, delaunay_remesh_frequency=0)
+
+    class _Planting(_Recorder):
+        def search(self, points, **kw):
+            self.mesh._native.mesh_key = (id(self.mesh), self.mesh.vertices.shape[0], int(self.mesh.faces.shape[0]), 20)
+            return _Recorder.search(self, points, **kw)
+    mm.ShrinkwrapMeshConjGrad = _Planting                           # (restored by the recorder fixture's monkeypatch)
+    m.shrink_wrap(np.zeros((5, 3), 'f4'), 10.0)
+    assert len(recorder.calls) == 1 and m._native.mesh_key is None  # the fit forgets that the device mirrors the mesh
+    # a matching key and a stale `fs` planted with no fit running: the remesher must start from the edited positions
+    stale = np.ascontiguousarray(m.vertices, np.float32).copy()
+    m.vertices[:] *= np.float32(1.1)
+    edited = np.array(m.vertices, np.float32)
+
+    class _CG(object):
+        fs = stale
+    m.cg = _CG()
+    m._native.mesh_key = (id(m), m.vertices.shape[0], int(m.faces.shape[0]), 20)
+    seen = []
+
+    def capture(v, f, n, t, l, r):
+        seen.append(np.array(v, np.float32))
+        return np.asarray(v, np.float32), np.asarray(f, np.int32), dict(mean_edge_length=1.0)
+    builtin_remesher(m, 1, 5.0, 0.5, 0, _remesh=capture)
+    assert len(seen) == 1 and np.array_equal(seen[0], edited) and not np.array_equal(seen[0], stale)
+    # ... while inside a fit the same planted state IS the shortcut (what the block boundary relies on)
+    m2 = _mesh()
+    m2.cg, m2._native = _CG(), type(m._native)()
+    m2._native.mesh_key = (id(m2), m2.vertices.shape[0], int(m2.faces.shape[0]), 20)
+    m2._in_fit = True
+    builtin_remesher(m2, 1, 5.0, 0.5, 0, _remesh=capture)
+    assert np.array_equal(seen[1], stale)

@@ -299,3 +299,79 @@ def test_fit_with_the_device_hole_puncher_finds_the_torus_hole():
     print('rms to the torus: with punching %.2f nm, without %.2f nm; chi %d' % (rms(a), rms(plain), euler(va, fa)))
     assert rms(a) < rms(plain)
     assert np.array_equal(va, np.asarray(b.vertices)) and np.array_equal(fa, np.asarray(b.faces))
+
+
+# ---- off the origin -------------------------------------------------------------------------------------------------------------------
+OFFSETS = {'offset_4e4': (4e4, 3e4, 1e3), 'offset_2e5': (2e5, -1.5e5, 1e5)}
+
+
+def _shift(a, offset):
+    return (np.asarray(a, np.float64) + np.asarray(OFFSETS[offset])).astype(F32)
+
+
+def _step1_scene(grid, offset):
+    """(localizations, vertices, faces, cell_size) of a step-1 case, translated"""
+    v, f = pancake(3, 400.0, 85.0)
+    pts = torus_cloud(n=40000)
+    cell = 0.0
+    if grid == 'quarter':
+        cell = 50.0 / 4
+    elif grid == 'triple':
+        cell = 3 * 50.0
+    elif grid == 'capped':
+        cell = 50.0 / 4                                               # with a far outlier: the axis would want 10^5 cells, the cap is 2048
+        pts = np.vstack([pts, [[1.5e6, 0.0, 0.0]]]).astype(F32)
+    elif grid == 'coplanar':
+        pts = pts.copy()
+        pts[:, 2] = F32(0.0)                                          # every localization in one plane through the mesh
+    elif grid == 'single':
+        pts = np.array([[300.0, 0.0, 60.0]], F32)
+    return _shift(pts, offset), _shift(v, offset), f, cell
+
+
+@pytest.mark.parametrize('offset', list(OFFSETS))
+@pytest.mark.parametrize('grid', ['auto', 'quarter', 'triple', 'capped', 'coplanar', 'single'])
+def test_candidate_faces_off_the_origin(grid, offset):
+    pts, v, f, cell = _step1_scene(grid, offset)
+    eps = 50.0
+    ctx = H.HolePunchContext(0)
+    ctx.set_points(pts, cell)
+    far, dist = ctx.empty_faces(v, f, eps, return_dist=True)
+    ref, d = restated_step1(v, f, pts, eps)
+    want = np.zeros(f.shape[0], bool)
+    want[ref] = True
+    ambiguous = np.abs(d - eps) <= 1e-5 * eps
+    print('%s %s: %d faces, %d candidates, %d ambiguous, %d mismatches outside the band'
+          % (grid, offset, f.shape[0], far.sum(), ambiguous.sum(), (far != want)[~ambiguous].sum()))
+    assert np.array_equal(far[~ambiguous], want[~ambiguous])
+    if grid == 'single':
+        assert 0 < far.sum() < f.shape[0]
+    ctx.close()
+
+
+@pytest.mark.parametrize('offset', list(OFFSETS))
+def test_pairing_and_prism_off_the_origin(offset):
+    """step 2 bit-identical to the float32 loop and step 3 equal to the float64 restatement, on the torus scene translated"""
+    pts = _shift(torus_cloud(n=100000), offset)
+    v0, f = pancake()
+    v = _shift(v0, offset)
+    eps = 50.0
+    nrm = face_geometry(v, f)
+    hc, _ = restated_step1(v, f, pts, eps)
+    ctx = H.HolePunchContext(0)
+    got_pairs = ctx.pair_faces(v, f, nrm, hc.astype('i4'))
+    ref_pairs = restated_pairs(v[f[hc]], nrm[hc])
+    print('%s: %d candidates, %d paired' % (offset, hc.size, (ref_pairs >= 0).sum()))
+    assert (ref_pairs >= 0).sum() > 0
+    assert np.array_equal(got_pairs, ref_pairs)
+    cands, cpair = H.pair_postprocess(hc.astype('i4'), ref_pairs)
+    ctx.set_points(pts)
+    rng = np.random.default_rng(4)
+    extra = rng.choice(f.shape[0], 300, replace=False).astype('i4')
+    for cc, pp in ((cands, cpair), (extra, rng.permutation(extra.size))):
+        got = ctx.prism_empty(v, f, nrm, cc, pp, eps)
+        ref, decide = restated_prism(v, f, nrm, cc, pp, pts, eps)
+        close = np.abs(decide) <= 1e-4
+        print('  %d pairs: %d empty, %d within 1e-4 nm of the threshold' % (cc.size, ref.sum(), close.sum()))
+        assert np.array_equal(got[~close], ref[~close])
+    ctx.close()

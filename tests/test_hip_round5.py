@@ -158,11 +158,11 @@ def test_attraction_step_toggled_at_run_time_gives_the_same_bits():
         assert np.array_equal(a, b) and np.array_equal(a, m)
 
 
-def test_curvature_tables_built_on_the_device_equal_the_host_substrates(monkeypatch):
+def test_curvature_tables_built_on_the_device_equal_the_host_substrates_and_the_in_fit_fast_path(monkeypatch):
     """nw_curvature with NULL tables builds nbr_next / nbr_area from the faces and positions on the device: every one of the twelve outputs
     must equal, bit for bit, the call with the tables the host substrate builds (remesh.ring_tables) -- on a closed mesh, on a mesh with a
     boundary (open fans) and with unused vertex slots; and the fast path of the block boundary (nothing uploaded: the block left the mesh
-    on the device) must give what a fresh upload of the same mesh gives."""
+    on the device), which is taken only while the fit runs, must give what a fresh upload of the same mesh gives."""
     from ch_shrinkwrap_amd import membrane_mesh as mm
     from ch_shrinkwrap_amd.trimesh import icosphere
     from ch_shrinkwrap_amd.synth import sphere_cloud
@@ -179,19 +179,28 @@ def test_curvature_tables_built_on_the_device_equal_the_host_substrates(monkeypa
             out[host] = [d.copy()] + [getattr(m, n).copy() for n in names]
         for a, b in zip(out['1'], out['0']):
             assert np.array_equal(a, b, equal_nan=True)
-    # the block boundary's fast path
+    # the block boundary's fast path: taken inside a fit only (afterwards the caller may have edited the mesh), so it is exercised from a
+    # hook the block boundary calls while the device still holds the block's positions and refreshed normals
     monkeypatch.setenv('NW_HOST_TABLES', '0')
     pts = sphere_cloud(20000, 100.0, 5.0, seed=2)
-    m = mm.MembraneMesh(v.copy(), f, kc=1.0, step_size=20.0, max_iter=5, remesh_frequency=0, delaunay_remesh_frequency=0)
+    m = mm.MembraneMesh(v.copy(), f, kc=1.0, step_size=20.0, max_iter=10, remesh_frequency=0, delaunay_remesh_frequency=5)
+    seen = []
+
+    def at_boundary(mesh, points, eps):
+        assert mesh._native.mesh_key is not None and mesh._native.mesh_key[0] == id(mesh)
+        key = mesh._native.mesh_key
+        d_fast = mesh.curvature_grad_c(dN=0.1)
+        assert mesh._native.mesh_key == key                           # nothing was uploaded
+        fast = [d_fast.copy()] + [getattr(mesh, n).copy() for n in names]
+        mesh._native.mesh_key = None                                  # forget that the device holds it: a fresh upload of positions and normals
+        d_up = mesh.curvature_grad_c(dN=0.1)
+        up = [d_up.copy()] + [getattr(mesh, n).copy() for n in names]
+        for a, b in zip(fast, up):
+            assert np.array_equal(a, b, equal_nan=True)
+        seen.append(len(seen))
+    m.hole_puncher = at_boundary
     m.shrink_wrap(pts, np.full(pts.shape, 5.0, 'f4'))
-    assert m._native.mesh_key is not None and m._native.mesh_key[0] == id(m)
-    d_fast = m.curvature_grad_c(dN=0.1)
-    fast = [d_fast.copy()] + [getattr(m, n).copy() for n in names]
-    m._native.mesh_key = None                                         # forget that the device holds it: a fresh upload of positions and normals
-    d_up = m.curvature_grad_c(dN=0.1)
-    up = [d_up.copy()] + [getattr(m, n).copy() for n in names]
-    for a, b in zip(fast, up):
-        assert np.array_equal(a, b, equal_nan=True)
+    assert seen == [0, 1] and m._native.mesh_key is None
 
 
 def test_driver_with_device_built_tables_follows_the_host_tables_fit(monkeypatch):

@@ -378,3 +378,178 @@ def test_recipe_fit_on_c4_cuts_nothing_with_the_defaults():
     assert all(r['cut'] == 0 for r in a.neck_log)
     assert np.array_equal(np.asarray(a.vertices), np.asarray(plain.vertices)) and np.array_equal(np.asarray(a.faces), np.asarray(plain.faces))
     assert sorted(genera(np.asarray(a.vertices), np.asarray(a.faces))) == sorted(genera(np.asarray(plain.vertices), np.asarray(plain.faces)))
+
+
+# ---- off the origin and degenerate inputs --------------------------------------------------------------------------------------------
+OFFSETS = {'origin': (0.0, 0.0, 0.0), 'offset_4e4': (4e4, 3e4, 1e3), 'offset_2e5': (2e5, -1.5e5, 1e5)}
+
+
+def _shifted(v, offset):
+    return (np.asarray(v, np.float64) + np.asarray(OFFSETS[offset])).astype(F32)
+
+
+def exact_volumes(v, f, lab, n):
+    """6 x signed volume per component as exact integers: every float32 coordinate is an integer multiple of 2^-s"""
+    vv = np.asarray(v, np.float64)
+    nz = vv[vv != 0]
+    s = int(max(0, (23 - (np.frexp(np.abs(nz))[1] - 1)).max())) if nz.size else 0
+    q = np.ldexp(vv, s).astype(object)
+    q = np.vectorize(int, otypes=[object])(q)
+    p0, p1, p2 = q[f[:, 0]], q[f[:, 1]], q[f[:, 2]]
+    det = (p0[:, 0] * (p1[:, 1] * p2[:, 2] - p1[:, 2] * p2[:, 1]) + p0[:, 1] * (p1[:, 2] * p2[:, 0] - p1[:, 0] * p2[:, 2])
+           + p0[:, 2] * (p1[:, 0] * p2[:, 1] - p1[:, 1] * p2[:, 0]))
+    out = []
+    for c in range(n):
+        out.append(sum(det[lab == c].tolist()))
+    return out, 3 * s
+
+
+def documented_volume_bound(v, f, lab, n):
+    """what include/nw_surgery.h promises: n_c 2^-k / 2 (+ |o|_1 n_c 2^-k' / 12) of the fixed point, plus the rounding of the float64 terms"""
+    vv = np.asarray(v, np.float64)
+    o = ((vv.min(0) + vv.max(0)) * 0.5).astype(F32).astype(np.float64)
+    M = max(np.abs(vv - o).max(), 1e-30)
+    scale = lambda bound: 2.0 ** np.floor(62.0 - np.log2(bound * max(f.shape[0], 1)))
+    sv, sn = scale(M ** 3), scale(12.0 * M * M)
+    q = vv[f] - o
+    term = (np.abs(q[:, 0]) * (np.abs(q[:, 1, [1, 2, 0]] * q[:, 2, [2, 0, 1]]) + np.abs(q[:, 1, [2, 0, 1]] * q[:, 2, [1, 2, 0]]))).sum(1) / 6.0
+    cross = np.abs(np.cross(q[:, 1] - q[:, 0], q[:, 2] - q[:, 0])).sum(1)
+    f64 = 8 * np.finfo(np.float64).eps * (term + np.abs(o).sum() * cross / 6.0)
+    nc = np.bincount(lab[lab >= 0], minlength=n)
+    return nc * (0.5 / sv + np.abs(o).sum() * 0.5 / sn / 6.0) + np.bincount(lab[lab >= 0], weights=f64[lab >= 0], minlength=n)
+
+
+def shell_scene():
+    """a small positively oriented shell outside a large mesh, a small inverted shell inside it, and the large mesh"""
+    big = sphere(5, 500.0)
+    small = sphere(1, 2.0, (520.0, 0.0, 0.0))
+    cavity = sphere(1, 2.0, (100.0, 0.0, 0.0))
+    return join(big, small, (cavity[0], np.ascontiguousarray(cavity[1][:, ::-1])))
+
+
+@pytest.mark.parametrize('offset', list(OFFSETS))
+def test_component_stats_off_the_origin_against_exact_arithmetic(ctx, offset):
+    v0, f = shell_scene()
+    v = _shifted(v0, offset)
+    tw = S.twins(f, v.shape[0])
+    lab, n = ctx.label_faces(f, tw)
+    assert n == 3
+    got = ctx.component_stats(v, f, tw, lab, n)
+    ref = restated_stats(v, f, tw, lab, n)
+    p = v.astype(np.float64)[f]
+    area = 0.5 * np.linalg.norm(np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]), axis=1)
+    ref_area = np.bincount(lab, weights=area, minlength=n)
+    six, e = exact_volumes(v, f, lab, n)
+    ref_vol = np.array([float(x) / 6.0 / 2.0 ** e for x in six])   # (the quotient rounded once)
+    bound = documented_volume_bound(v, f, lab, n)
+    err = np.abs(got['volume'] - ref_vol)
+    print('%s: volumes %s; error %s; documented bound %s; area error %s'
+          % (offset, got['volume'], err, bound, np.abs(got['area'] - ref_area)))
+    assert np.array_equal(got['faces'], ref['faces']) and np.array_equal(got['border'], ref['border'])
+    assert (err <= bound).all()
+    # area: n_c 2^-k / 2 with 2^k = 2^62 / (n_faces 6 M^2), plus float64 rounding of the terms
+    vv = v.astype(np.float64)
+    M = np.abs(vv - ((vv.min(0) + vv.max(0)) * 0.5).astype(F32)).max()
+    s_area = 2.0 ** np.floor(62.0 - np.log2(6.0 * M * M * f.shape[0]))
+    area_bound = np.bincount(lab, minlength=n) * 0.5 / s_area + 1e-14 * ref_area
+    print('  area error %s, documented bound %s' % (np.abs(got['area'] - ref_area), area_bound))
+    assert (np.abs(got['area'] - ref_area) <= area_bound).all()
+    assert got['volume'][1] > 0 > got['volume'][2]                  # the signs remove_inner_surfaces decides on
+    for c in range(n):
+        vv = v[np.unique(f[lab == c])]
+        assert np.array_equal(got['bbox'][c], np.concatenate([vv.min(0), vv.max(0)]))
+
+
+def test_remove_inner_surfaces_decides_the_same_off_the_origin():
+    v0, f = shell_scene()
+    decided = {}
+    for offset in OFFSETS:
+        m = MembraneMesh(_shifted(v0, offset), f)
+        decided[offset] = (m.remove_inner_surfaces(), np.asarray(m.faces).copy())
+    print({k: r for k, (r, _) in decided.items()})
+    assert [c for c, _ in decided['origin'][0]] == [2] and 'inverted' in decided['origin'][0][0][1]
+    kind = lambda removed: [(c, 'inverted' in r, 'inside' in r) for c, r in removed]
+    for offset in OFFSETS:
+        assert kind(decided[offset][0]) == kind(decided['origin'][0]), offset
+        assert np.array_equal(decided[offset][1], decided['origin'][1]), offset
+
+
+def _short_edge_reference(v, f, threshold):
+    el = TriMesh(v, f)._edge_lengths()
+    med = np.median(el)
+    thr = F32(threshold) * med
+    ref = np.zeros(v.shape[0], bool)
+    ref[f[:, [1, 2, 0]].ravel()[el < thr]] = True
+    return ref, med
+
+
+def _grid(n=6, h=2.0):
+    xx, yy = np.meshgrid(np.arange(n, dtype='f4') * F32(h), np.arange(n, dtype='f4') * F32(h), indexing='ij')
+    v = np.stack([xx.ravel(), yy.ravel(), np.zeros(n * n, 'f4')], 1)
+    idx = np.arange(n * n).reshape(n, n)
+    a, b, c, d = idx[:-1, :-1].ravel(), idx[1:, :-1].ravel(), idx[1:, 1:].ravel(), idx[:-1, 1:].ravel()
+    return v, np.concatenate([np.stack([a, b, c], 1), np.stack([a, c, d], 1)], 0).astype(np.int32)
+
+
+def _short_edge_case(case):
+    if case in OFFSETS:
+        v, f = sphere(3, 100.0)
+        v = v + np.random.default_rng(5).normal(scale=0.3, size=v.shape).astype(F32)
+        return _shifted(v, case), f
+    if case == 'one_face':
+        return np.array([[0, 0, 0], [3, 0, 0], [0, 4, 0]], F32), np.array([[0, 1, 2]], np.int32)
+    if case == 'two_faces':
+        return np.array([[0, 0, 0], [3, 0, 0], [0, 4, 0], [3, 5, 1]], F32), np.array([[0, 1, 2], [1, 3, 2]], np.int32)
+    if case == 'ties':
+        return _grid()                                               # two lengths, each many times: the median is a tie
+    if case == 'zero_length':
+        v, f = _grid()
+        v = v.copy()
+        v[7] = v[8]                                                  # duplicated positions: edges of length exactly 0
+        v[20] = v[14]
+        return v, f
+    raise KeyError(case)
+
+
+@pytest.mark.parametrize('case', list(OFFSETS) + ['one_face', 'two_faces', 'ties', 'zero_length'])
+def test_short_edge_selection_equals_numpy_on_edge_cases(ctx, case):
+    v, f = _short_edge_case(case)
+    for threshold in (0.05, 0.0, 0.75, 1e30):
+        ref, med = _short_edge_reference(v, f, threshold)
+        flags, got_med = ctx.short_edge_vertices(v, f, threshold)
+        assert got_med == med and got_med.dtype == np.float32, (case, threshold)
+        assert np.array_equal(flags, ref), (case, threshold)
+        if threshold == 0.0:
+            assert not flags.any()
+        if threshold == 1e30:
+            assert np.array_equal(flags, np.isin(np.arange(v.shape[0]), f))     # every head of a half-edge
+    if case == 'zero_length':
+        assert _short_edge_reference(v, f, 0.05)[0][[7, 8, 14, 20]].sum() >= 2
+
+
+@pytest.mark.parametrize('case', ['single_face', 'empty_mask', 'twins_excluded'])
+def test_labels_equal_scipy_on_degenerate_masks(ctx, case):
+    if case == 'single_face':
+        f = np.array([[0, 1, 2]], np.int32)
+        tw, mask = S.twins(f, 3), None
+    else:
+        v, f = sphere(2, 10.0)
+        tw = S.twins(f, v.shape[0])
+        if case == 'empty_mask':
+            mask = np.zeros(f.shape[0], np.uint8)
+        else:
+            # include a face set, exclude every twin face of it (those not themselves included): the included faces touch only excluded ones
+            inc = np.zeros(f.shape[0], bool)
+            for g in range(f.shape[0]):
+                if not inc[np.maximum(tw[3 * g: 3 * g + 3], 0) // 3].any():
+                    inc[g] = True
+            mask = inc.astype(np.uint8)
+    got, n = ctx.label_faces(f, tw, mask)
+    ref, nr = S.scipy_label_faces(f, tw, mask)
+    assert n == nr and np.array_equal(got, ref)
+    if case == 'single_face':
+        assert n == 1 and got.tolist() == [0]
+    if case == 'empty_mask':
+        assert n == 0 and (got == -1).all()
+    if case == 'twins_excluded':
+        assert n == int(mask.sum()) > 1                               # every included face is a component of its own
