@@ -117,6 +117,56 @@ def load():
     return L
 
 
+def load_entry_points(symbols, argtypes, abi_symbol, abi_version, what):
+    """One of the library's other C-ABIs (the same .so as include/nanowrap.h's; load() first, so that the HIP runtime order holds):
+    a CDLL with every name of `symbols` checked, `argtypes[name]` set, `*_destroy` returning nothing, `*_last_error` a string and
+    everything else an int, and `abi_symbol()` equal to `abi_version`."""
+    load()
+    L = ctypes.CDLL(LIB_PATH)                # (own function objects: argtypes here do not touch load()'s)
+    for s in symbols:
+        if not hasattr(L, s):
+            raise RuntimeError('%s does not export %s: rebuild it (python -m ch_shrinkwrap_amd.build)' % (LIB_PATH, s))
+        fn = getattr(L, s)
+        fn.argtypes = argtypes[s]
+        fn.restype = None if s.endswith('_destroy') else ctypes.c_char_p if s.endswith('_last_error') else ctypes.c_int
+    if getattr(L, abi_symbol)() != abi_version:
+        raise RuntimeError('%s ABI %d, expected %d: rebuild the library' % (what, getattr(L, abi_symbol)(), abi_version))
+    return L
+
+
+def mesh_arrays(pos, faces):
+    return np.ascontiguousarray(pos, np.float32).reshape(-1, 3), np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+
+
+class QueryContext(object):
+    """Base of the block-boundary query contexts: one <prefix>ctx of the library.  A subclass sets `prefix` ('nwh_'), `errors` (status ->
+    text), `gpu_only` (what its create failure says runs on the GPU only) and `load` (its module's load())."""
+    prefix = errors = gpu_only = load = None
+
+    def __init__(self, device=0):
+        self.L = self.load()
+        self.h = ctypes.c_void_p()
+        code = getattr(self.L, self.prefix + 'create')(int(device), ctypes.byref(self.h))
+        if code != 0:
+            raise RuntimeError('%screate failed: %s -- %s on the GPU only' % (self.prefix, self.errors.get(code, code), self.gpu_only))
+
+    def check(self, code, what):
+        if code != 0:
+            msg = getattr(self.L, self.prefix + 'last_error')(self.h) if self.h else b''
+            raise RuntimeError('%s: %s %s' % (what, self.errors.get(code, 'error %d' % code), (msg or b'').decode()))
+
+    def close(self):
+        if self.h:
+            getattr(self.L, self.prefix + 'destroy')(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 _hip = None
 
 

@@ -1,36 +1,55 @@
 """
 Builds the native pieces in-tree (no pip, no JIT cache):
-  * ch_shrinkwrap_amd/libnanowrap_hip.so  -- the HIP kernels + C-ABI (hipcc, --offload-arch=gfx950): csrc/nanowrap.hip, nw_sort.hip, nw_remesh_dev.hip,
-                                            nw_holepunch.hip (include/nw_holepunch.h), nw_surgery.hip (include/nw_surgery.h)
+  * ch_shrinkwrap_amd/libnanowrap_hip.so  -- the HIP kernels + C-ABI (hipcc, --offload-arch=gfx950): one object per row of UNITS below
   * ch_shrinkwrap_amd/libnw_remesh.so     -- the block-boundary remesher (host C++, g++; include/nw_remesh.h)
 The oracle (test infrastructure) is built by oracle/Makefile, see __graft_entry__.build().
 """
+import glob
 import os
 import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, 'libnanowrap_hip.so')
-SRC = os.path.join(HERE, 'csrc', 'nanowrap.hip')
-SRC_SORT = os.path.join(HERE, 'csrc', 'nw_sort.hip')      # set-up radix sort (hipCUB), its own translation unit
-OBJ_SORT = os.path.join(HERE, 'csrc', 'nw_sort.o')
-OBJ_MAIN = os.path.join(HERE, 'csrc', 'nanowrap.o')
-SRC_REMESH = os.path.join(HERE, 'csrc', 'nw_remesh_dev.hip')   # the block-boundary remesher as kernels (hipCUB scans), its own translation unit
-OBJ_REMESH = os.path.join(HERE, 'csrc', 'nw_remesh_dev.o')
-SRC_HOLEPUNCH = os.path.join(HERE, 'csrc', 'nw_holepunch.hip')  # the hole-punch point queries (include/nw_holepunch.h), its own translation unit
-OBJ_HOLEPUNCH = os.path.join(HERE, 'csrc', 'nw_holepunch.o')
-HDR_HOLEPUNCH = os.path.join(os.path.dirname(HERE), 'include', 'nw_holepunch.h')
-SRC_SURGERY = os.path.join(HERE, 'csrc', 'nw_surgery.hip')      # the neck / short-edge / inner-surface queries (include/nw_surgery.h), its own translation unit
-OBJ_SURGERY = os.path.join(HERE, 'csrc', 'nw_surgery.o')
-HDR_SURGERY = os.path.join(os.path.dirname(HERE), 'include', 'nw_surgery.h')
-import glob
-# every header of csrc/ is included by nanowrap.hip (directly or through nw_kernels.h): editing any of them must rebuild the library
-DEPS = [SRC, SRC_SORT, SRC_REMESH, SRC_HOLEPUNCH, HDR_HOLEPUNCH, SRC_SURGERY, HDR_SURGERY] + sorted(glob.glob(os.path.join(HERE, 'csrc', '*.h'))) + [os.path.join(os.path.dirname(HERE), 'include', 'nanowrap.h')]
+
+
+def _csrc(name):
+    return os.path.join(HERE, 'csrc', name)
+
+
+def _include(name):
+    return os.path.join(os.path.dirname(HERE), 'include', name)
+
 
 # -ffp-contract=off : the parity-critical float32 arithmetic must round products before adding, exactly like
 #                     the NumPy reference (explicit fma() is used where contraction is wanted);
 # -munsafe-fp-atomics: float/double atomicAdd -> global_atomic_add_f32/f64 (no CAS loop).
 HIPCC_FLAGS = ['-O3', '--offload-arch=gfx950', '-fPIC', '-shared', '-ffp-contract=off', '-munsafe-fp-atomics',
                '-fvisibility=hidden', '-Wall', '-Wno-unused-function']
+_BASE = ['-O3', '--offload-arch=gfx950', '-fPIC', '-fvisibility=hidden']
+# the block-boundary query units: no contraction, as the pairing kernel and the half-edge lengths must round every product as the
+# reference's C loop and TriMesh's NumPy do (their results are bit-identical)
+_QUERY = _BASE + ['-ffp-contract=off', '-Wall', '-Wno-unused-function']
+_BQ = [_csrc('nw_bq.h'), _csrc('nw_device.h')]            # (nw_device.h: nw_wave_incl_scan)
+
+OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_BQ = _csrc('nanowrap.o'), _csrc('nw_holepunch.o'), _csrc('nw_surgery.o'), _csrc('nw_bq.o')
+# the translation units of libnanowrap_hip.so: (source, object, what else it is rebuilt for, flags).  The objects are linked in this order.
+UNITS = [
+    # the per-iteration kernels and the C-ABI; every header of csrc/ but nw_bq.h is included by it (directly or through nw_kernels.h)
+    (_csrc('nanowrap.hip'), OBJ_MAIN, sorted(set(glob.glob(_csrc('*.h'))) - {_csrc('nw_bq.h')}) + [_include('nanowrap.h')],
+     [f for f in HIPCC_FLAGS if f != '-shared']),
+    # set-up radix sort (hipCUB)
+    (_csrc('nw_sort.hip'), _csrc('nw_sort.o'), [], _BASE + ['-Wno-unused-value']),
+    # the block-boundary remesher as kernels (hipCUB scans)
+    (_csrc('nw_remesh_dev.hip'), _csrc('nw_remesh_dev.o'), [_include('nanowrap.h')],
+     _BASE + ['-ffp-contract=off', '-Wall', '-Wno-unused-value', '-Wno-unused-function']),
+    # the hole-punch point queries
+    (_csrc('nw_holepunch.hip'), OBJ_HOLEPUNCH, [_include('nw_holepunch.h'), _csrc('nw_bq.h')], _QUERY),
+    # the neck / short-edge / inner-surface queries
+    (_csrc('nw_surgery.hip'), OBJ_SURGERY, [_include('nw_surgery.h')] + _BQ, _QUERY),
+    # what the two above share (csrc/nw_bq.h): the exclusive scan
+    (_csrc('nw_bq.hip'), OBJ_BQ, _BQ, _QUERY),
+]
+DEPS = sorted(set(d for src, _, extra, _ in UNITS for d in [src] + extra))
 
 
 def needs_build():
@@ -50,22 +69,11 @@ def build_hip_library(force=False, verbose=False):
             print(' '.join(cmd))
         subprocess.check_call(cmd)
 
-    if force or not os.path.exists(OBJ_SORT) or os.path.getmtime(OBJ_SORT) < os.path.getmtime(SRC_SORT):
-        run([hipcc, '-O3', '--offload-arch=gfx950', '-fPIC', '-fvisibility=hidden', '-Wno-unused-value', '-c', '-o', OBJ_SORT, SRC_SORT])
-    if force or not os.path.exists(OBJ_REMESH) or os.path.getmtime(OBJ_REMESH) < max(os.path.getmtime(SRC_REMESH), os.path.getmtime(DEPS[-1])):
-        run([hipcc, '-O3', '--offload-arch=gfx950', '-fPIC', '-fvisibility=hidden', '-ffp-contract=off', '-Wall', '-Wno-unused-value', '-Wno-unused-function',
-             '-c', '-o', OBJ_REMESH, SRC_REMESH])
-    if force or not os.path.exists(OBJ_HOLEPUNCH) or os.path.getmtime(OBJ_HOLEPUNCH) < max(os.path.getmtime(SRC_HOLEPUNCH), os.path.getmtime(HDR_HOLEPUNCH)):
-        # (-ffp-contract=off: the pairing kernel must round every product as the reference's C loop does -- its result is bit-identical)
-        run([hipcc, '-O3', '--offload-arch=gfx950', '-fPIC', '-fvisibility=hidden', '-ffp-contract=off', '-Wall', '-Wno-unused-function',
-             '-c', '-o', OBJ_HOLEPUNCH, SRC_HOLEPUNCH])
-    if force or not os.path.exists(OBJ_SURGERY) or os.path.getmtime(OBJ_SURGERY) < max(os.path.getmtime(SRC_SURGERY), os.path.getmtime(HDR_SURGERY)):
-        # (-ffp-contract=off: the half-edge lengths must round every product as TriMesh's do -- the short-edge selection is bit-identical)
-        run([hipcc, '-O3', '--offload-arch=gfx950', '-fPIC', '-fvisibility=hidden', '-ffp-contract=off', '-Wall', '-Wno-unused-function',
-             '-c', '-o', OBJ_SURGERY, SRC_SURGERY])
-    run([hipcc] + [f for f in HIPCC_FLAGS if f != '-shared'] + ['-c', '-o', OBJ_MAIN, SRC])
+    for src, obj, extra, flags in UNITS:
+        if force or not os.path.exists(obj) or os.path.getmtime(obj) < max(os.path.getmtime(d) for d in [src] + extra):
+            run([hipcc] + flags + ['-c', '-o', obj, src])
     check_kernel_budgets(verbose=verbose)          # before the link: a kernel that spills or outgrows its occupancy never ships
-    run([hipcc, '--offload-arch=gfx950', '-fPIC', '-shared', '-o', LIB, OBJ_MAIN, OBJ_SORT, OBJ_REMESH, OBJ_HOLEPUNCH, OBJ_SURGERY])
+    run([hipcc, '--offload-arch=gfx950', '-fPIC', '-shared', '-o', LIB] + [obj for _, obj, _, _ in UNITS])
     return LIB
 
 
@@ -93,9 +101,6 @@ KERNEL_BUDGETS = {
     'k_hp_prism':                     (176, 0),            # six float64 half-planes and two centres live across the cell walk (3 waves per SIMD)
     'k_hp_cell_count':                (32, 0),
     'k_hp_scatter':                   (32, 0),
-    'k_hp_scan_final':                (64, 1024),
-    'k_hp_scan_tiles':                (32, 1024),
-    'k_hp_scan_bsums':                (64, 1024),
     'k_hp_bbox':                      (32, 0),
     'k_hp_cand_geom':                 (32, 0),
     'k_hp_pair_final':                (16, 0),
@@ -104,9 +109,6 @@ KERNEL_BUDGETS = {
     'k_ws_hook':                      (32, 0),
     'k_ws_compress':                  (16, 0),
     'k_ws_number':                    (16, 0),
-    'k_ws_scan_tiles':                (32, 1024),
-    'k_ws_scan_bsums':                (32, 1024),
-    'k_ws_scan_final':                (32, 1024),
     'k_ws_stats':                     (64, 0),
     'k_ws_bbox_init':                 (16, 0),
     'k_ws_active':                    (16, 0),
@@ -115,8 +117,12 @@ KERNEL_BUDGETS = {
     'k_ws_hist':                      (16, 2048),          # two 256-bin histograms
     'k_ws_pick':                      (32, 0),
     'k_ws_flag':                      (16, 0),
+    # the exclusive scan both share (csrc/nw_bq.o)
+    'k_bq_scan_tiles':                (32, 1024),
+    'k_bq_scan_bsums':                (32, 1024),
+    'k_bq_scan_final':                (32, 1024),
 }
-BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY]
+BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_BQ]
 
 
 def kernel_resources(obj=None):

@@ -5,6 +5,7 @@
 //   step 2  which opposite candidate face is nearest "in mean-normal space"     (membrane_mesh_utils.c:1301-1376, a serial O(C^2) loop)
 //   step 3  is the prism between a pair of faces empty of localizations         (:946-1016, query_ball_point + six half-plane tests)
 // Here they are kernels over one cell grid of the localizations, built once per fit by a counting sort (count, exclusive scan, scatter).
+// The scan, the device buffer and the context's scaffolding are the block-boundary units' shared ones (nw_bq.h).
 //
 //   k_hp_empty_faces  one thread per face: the rows of cells that overlap the eps-ball, first localization within eps ends the search
 //                     (unless the nearest distance was asked for);
@@ -18,7 +19,6 @@
 // All stores are vector stores; no kernel uses scratch (build.py's KERNEL_BUDGETS checks it).
 #include <hip/hip_runtime.h>
 #include <cstdint>
-#include <cstring>
 #include <cmath>
 #include <climits>
 #include <string>
@@ -26,10 +26,10 @@
 #include <algorithm>
 
 #include "../../include/nw_holepunch.h"
+#include "nw_bq.h"
 
 #define NWH_EXPORT extern "C" __attribute__((visibility("default")))
 #define NWH_BLOCK 256
-#define NWH_SCAN_TILE 2048          // 256 threads x 8 (the tile of the library's k_scan_final)
 #define NWH_PAIR_CHUNK 4096         // j range of one k_hp_pair workgroup
 
 typedef unsigned long long u64;
@@ -48,12 +48,6 @@ __device__ __forceinline__ int hp_cell_1d(float x, float lo, float h, int dim)
     return (int)fminf(fmaxf(t, 0.0f), (float)(dim - 1));
 }
 
-__device__ __forceinline__ int hp_ord(float f)           // monotone float -> int map (atomicMin / atomicMax on floats)
-{
-    const int i = __float_as_int(f);
-    return i >= 0 ? i : i ^ 0x7fffffff;
-}
-
 __global__ __launch_bounds__(NWH_BLOCK) void k_hp_bbox(const float *__restrict__ xyz, int n, int *__restrict__ mm /* [7]: min xyz, max xyz, nonfinite */)
 {
     int lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {INT_MIN, INT_MIN, INT_MIN};
@@ -63,8 +57,8 @@ __global__ __launch_bounds__(NWH_BLOCK) void k_hp_bbox(const float *__restrict__
         for (int d = 0; d < 3; ++d) {
             const float x = xyz[3 * (int64_t)i + d];
             if (!isfinite(x)) { bad = 1; continue; }
-            lo[d] = min(lo[d], hp_ord(x));
-            hi[d] = max(hi[d], hp_ord(x));
+            lo[d] = min(lo[d], bq::enc_ord(x));
+            hi[d] = max(hi[d], bq::enc_ord(x));
         }
     }
 #pragma unroll
@@ -96,76 +90,6 @@ __global__ __launch_bounds__(NWH_BLOCK) void k_hp_scatter(const float *__restric
     if (i >= n) return;
     const int slot = atomicAdd(&cursor[cell[i]], 1);       // (order inside a cell is arbitrary: every query is an existence / minimum test)
     sorted[slot] = make_float4(xyz[3 * (int64_t)i], xyz[3 * (int64_t)i + 1], xyz[3 * (int64_t)i + 2], 0.0f);
-}
-
-// ---- exclusive scan of the cell counts: out[0..n] with out[n] = total (the library's three-launch scan, nw_kernels.h) ---------------
-__device__ __forceinline__ int hp_wave_incl_scan(int v, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-
-__global__ __launch_bounds__(NWH_BLOCK) void k_hp_scan_tiles(const int *__restrict__ in, int n, int *__restrict__ bsum)
-{
-    __shared__ int s_w[4];
-    const int base = blockIdx.x * NWH_SCAN_TILE + threadIdx.x * 8;
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s += (base + k < n) ? in[base + k] : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) bsum[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-
-__global__ __launch_bounds__(1024) void k_hp_scan_bsums(int *__restrict__ bsum, int nb)
-{
-    __shared__ int s_w[16];
-    __shared__ int s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int base = 0; base < nb; base += 1024) {
-        const int i = base + threadIdx.x;
-        const int v = i < nb ? bsum[i] : 0;
-        const int inc = hp_wave_incl_scan(v, lane);
-        if (lane == 63) s_w[wv] = inc;
-        __syncthreads();
-        int woff = 0;
-        for (int w = 0; w < wv; ++w) woff += s_w[w];
-        const int carry = s_carry;
-        if (i < nb) bsum[i] = carry + woff + inc - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = carry + woff + inc;
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(NWH_BLOCK) void k_hp_scan_final(const int *__restrict__ in, int n, const int *__restrict__ bsum, int *__restrict__ out)
-{
-    __shared__ int s_w[4];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int base = blockIdx.x * NWH_SCAN_TILE + threadIdx.x * 8;
-    int v[8];
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { v[k] = (base + k < n) ? in[base + k] : 0; s += v[k]; }
-    const int inc = hp_wave_incl_scan(s, lane);
-    if (lane == 63) s_w[wv] = inc;
-    __syncthreads();
-    int off = bsum[blockIdx.x] + inc - s;
-    for (int w = 0; w < wv; ++w) off += s_w[w];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        if (base + k < n) out[base + k] = off;
-        off += v[k];
-        if (base + k == n - 1) out[n] = off;
-    }
 }
 
 // ---- step 1: faces with no localization within eps of their centroid ---------------------------------------------------------------
@@ -455,29 +379,11 @@ __global__ __launch_bounds__(NWH_BLOCK) void k_hp_prism(const float *__restrict_
 // =====================================================================================================================================
 // host side
 // =====================================================================================================================================
-namespace {
+using bq::DevBuf;
+using bq::fail;
+using bq::nblk;
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    hipError_t ensure(size_t b)
-    {
-        if (b <= bytes && p) return hipSuccess;
-        if (p) { (void)hipFree(p); p = nullptr; bytes = 0; }
-        const hipError_t e = hipMalloc(&p, std::max<size_t>(b, 256));
-        if (e == hipSuccess) bytes = std::max<size_t>(b, 256);
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-    template <class T> T *as() const { return (T *)p; }
-};
-
-}  // namespace
-
-struct nwh_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
+struct nwh_ctx : bq::Ctx {
     // the grid of the localizations (nwh_set_points)
     int n_points = 0;
     int64_t n_cells = 0;
@@ -489,31 +395,7 @@ struct nwh_ctx {
 
 namespace {
 
-int fail(nwh_ctx *ctx, int code, const std::string &msg)
-{
-    if (ctx) ctx->err = msg;
-    return code;
-}
-
-#define NWH_HIP(call)                                                                                          \
-    do {                                                                                                       \
-        hipError_t e_ = (call);                                                                                \
-        if (e_ != hipSuccess)                                                                                  \
-            return fail(ctx, e_ == hipErrorOutOfMemory ? NWH_ERR_NOMEM : NWH_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-inline int nblk(int64_t n, int b = NWH_BLOCK) { return (int)((n + b - 1) / b); }
-
-// host-side checks of the mesh arguments (before any HIP call)
-int check_mesh(const float *pos, int64_t nv, const int32_t *faces, int64_t nf)
-{
-    if (!pos || !faces || nv < 3 || nf < 1 || nv > (1ll << 30) || nf > (1ll << 29)) return NWH_ERR_BADARG;
-    for (int64_t i = 0; i < 3 * nv; ++i)
-        if (!std::isfinite(pos[i])) return NWH_ERR_BADARG;
-    for (int64_t i = 0; i < 3 * nf; ++i)
-        if (faces[i] < 0 || faces[i] >= nv) return NWH_ERR_BADARG;
-    return NWH_OK;
-}
+#define NWH_HIP(call) BQ_HIP(call, NWH_ERR_NOMEM, NWH_ERR_HIP)
 
 int check_cands(const int32_t *cands, int64_t nc, int64_t nf)
 {
@@ -536,50 +418,15 @@ void gather(const float *pos, const int32_t *faces, const float *fn, const int32
     }
 }
 
-int scan_exclusive(nwh_ctx *ctx, const int *in, int n, int *out, DevBuf &tmp)
-{
-    const int nb = (n + NWH_SCAN_TILE - 1) / NWH_SCAN_TILE;
-    NWH_HIP(tmp.ensure(sizeof(int) * (size_t)(nb + 1)));
-    hipLaunchKernelGGL(k_hp_scan_tiles, dim3(nb), dim3(NWH_BLOCK), 0, ctx->stream, in, n, tmp.as<int>());
-    hipLaunchKernelGGL(k_hp_scan_bsums, dim3(1), dim3(1024), 0, ctx->stream, tmp.as<int>(), nb);
-    hipLaunchKernelGGL(k_hp_scan_final, dim3(nb), dim3(NWH_BLOCK), 0, ctx->stream, in, n, tmp.as<int>(), out);
-    NWH_HIP(hipGetLastError());
-    return NWH_OK;
-}
-
-float dec_ord(int v) { const int i = v >= 0 ? v : v ^ 0x7fffffff; float f; std::memcpy(&f, &i, 4); return f; }
-
 }  // namespace
 
 NWH_EXPORT int nwh_abi_version(void) { return NWH_ABI_VERSION; }
 
-NWH_EXPORT int nwh_create(int device, nwh_ctx **out)
-{
-    if (!out || device < 0) return NWH_ERR_BADARG;
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return NWH_ERR_HIP;
-    if (device >= ndev) return NWH_ERR_BADARG;
-    if (hipSetDevice(device) != hipSuccess) return NWH_ERR_HIP;
-    nwh_ctx *ctx = new nwh_ctx();
-    ctx->device = device;
-    if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { delete ctx; return NWH_ERR_HIP; }
-    *out = ctx;
-    return NWH_OK;
-}
+NWH_EXPORT int nwh_create(int device, nwh_ctx **out) { return bq::create(device, out, NWH_ERR_BADARG, NWH_ERR_HIP); }
 
-NWH_EXPORT void nwh_destroy(nwh_ctx *ctx)
-{
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    ctx->pts.release(); ctx->cstart.release();
-    ctx->a.release(); ctx->b.release(); ctx->c.release(); ctx->d.release(); ctx->e.release(); ctx->f.release();
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
-}
+NWH_EXPORT void nwh_destroy(nwh_ctx *ctx) { bq::destroy(ctx); }
 
-NWH_EXPORT const char *nwh_last_error(nwh_ctx *ctx) { return ctx ? ctx->err.c_str() : "null ctx"; }
+NWH_EXPORT const char *nwh_last_error(nwh_ctx *ctx) { return bq::last_error(ctx); }
 
 NWH_EXPORT int nwh_set_points(nwh_ctx *ctx, const float *xyz, int64_t n_points, float cell_size)
 {
@@ -610,7 +457,7 @@ NWH_EXPORT int nwh_set_points(nwh_ctx *ctx, const float *xyz, int64_t n_points, 
     if (mm[6]) return fail(ctx, NWH_ERR_NONFINITE, "nwh_set_points: a localization is not finite");
     float lo[3], ext[3];
     float emax = 0.0f;
-    for (int d = 0; d < 3; ++d) { lo[d] = dec_ord(mm[d]); ext[d] = dec_ord(mm[3 + d]) - lo[d]; emax = std::max(emax, ext[d]); }
+    for (int d = 0; d < 3; ++d) { lo[d] = bq::dec_ord(mm[d]); ext[d] = bq::dec_ord(mm[3 + d]) - lo[d]; emax = std::max(emax, ext[d]); }
     emax = std::max(emax, 1e-3f);
     // cell size: about one localization per cell of the box (the flattest axis counts as a thousandth of the widest), then widened until the
     // grid has at most max(4 n, 65536) cells and no axis more than 2048
@@ -638,8 +485,7 @@ NWH_EXPORT int nwh_set_points(nwh_ctx *ctx, const float *xyz, int64_t n_points, 
     NWH_HIP(hipMemsetAsync(ctx->d.p, 0, sizeof(int) * (size_t)(ncell + 1), ctx->stream));
     hipLaunchKernelGGL(k_hp_cell_count, dim3(nblk(n)), dim3(NWH_BLOCK), 0, ctx->stream, src, n, g, ctx->c.as<int>(), ctx->d.as<int>());
     NWH_HIP(hipGetLastError());
-    const int sc = scan_exclusive(ctx, ctx->d.as<int>(), (int)ncell, ctx->cstart.as<int>(), ctx->e);
-    if (sc != NWH_OK) return sc;
+    NWH_HIP(bq::scan_exclusive(ctx->stream, ctx->d.as<int>(), (int)ncell, ctx->cstart.as<int>(), ctx->e));
     NWH_HIP(hipMemcpyAsync(ctx->d.p, ctx->cstart.p, sizeof(int) * (size_t)ncell, hipMemcpyDeviceToDevice, ctx->stream));
     hipLaunchKernelGGL(k_hp_scatter, dim3(nblk(n)), dim3(NWH_BLOCK), 0, ctx->stream, src, n, ctx->c.as<int>(), ctx->d.as<int>(), ctx->pts.as<float4>());
     NWH_HIP(hipGetLastError());
@@ -657,8 +503,7 @@ NWH_EXPORT int nwh_empty_faces(nwh_ctx *ctx, const float *pos, int64_t n_vertice
                                uint8_t *far, float *dist)
 {
     if (!far || !(eps > 0.0f) || !std::isfinite(eps)) return NWH_ERR_BADARG;
-    const int cm = check_mesh(pos, n_vertices, faces, n_faces);
-    if (cm != NWH_OK) return cm;
+    if (!bq::mesh_ok(pos, n_vertices, faces, n_faces)) return NWH_ERR_BADARG;
     if (!ctx) return NWH_ERR_BADARG;
     if (ctx->n_points < 1) return fail(ctx, NWH_ERR_NOPOINTS, "nwh_empty_faces: nwh_set_points first");
     NWH_HIP(hipSetDevice(ctx->device));
@@ -683,8 +528,8 @@ NWH_EXPORT int nwh_pair_faces(nwh_ctx *ctx, const float *pos, int64_t n_vertices
                               const int32_t *cands, int64_t n_cands, int32_t *pairs)
 {
     if (!face_normals || !pairs) return NWH_ERR_BADARG;
-    int r = check_mesh(pos, n_vertices, faces, n_faces);
-    if (r == NWH_OK) r = check_cands(cands, n_cands, n_faces);
+    if (!bq::mesh_ok(pos, n_vertices, faces, n_faces)) return NWH_ERR_BADARG;
+    const int r = check_cands(cands, n_cands, n_faces);
     if (r != NWH_OK) return r;
     if (!ctx) return NWH_ERR_BADARG;
     NWH_HIP(hipSetDevice(ctx->device));
@@ -714,8 +559,8 @@ NWH_EXPORT int nwh_prism_empty(nwh_ctx *ctx, const float *pos, int64_t n_vertice
                                const int32_t *cands, const int32_t *pair_idx, int64_t n, float eps, uint8_t *empty)
 {
     if (!face_normals || !pair_idx || !empty || !(eps > 0.0f) || !std::isfinite(eps)) return NWH_ERR_BADARG;
-    int r = check_mesh(pos, n_vertices, faces, n_faces);
-    if (r == NWH_OK) r = check_cands(cands, n, n_faces);
+    if (!bq::mesh_ok(pos, n_vertices, faces, n_faces)) return NWH_ERR_BADARG;
+    const int r = check_cands(cands, n, n_faces);
     if (r != NWH_OK) return r;
     for (int64_t k = 0; k < n; ++k)
         if (pair_idx[k] < 0 || pair_idx[k] >= n) return NWH_ERR_BADARG;

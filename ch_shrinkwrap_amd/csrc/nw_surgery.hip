@@ -5,8 +5,8 @@
 //   k_ws_init / k_ws_hook / k_ws_compress   union-find over the twin table (ECL-CC): a face hooks the larger of two roots onto the smaller
 //                                           with atomicCAS, so every root is its component's minimum face id whatever the schedule; one
 //                                           hooking launch, however long the component (no propagation rounds);
-//   k_ws_scan_* + k_ws_number               roots are flagged, scanned (the three-launch scan of nw_holepunch.hip) and every face takes
-//                                           its root's rank: labels in order of the components' smallest face ids;
+//   bq::scan_exclusive + k_ws_number        roots are flagged, scanned (the block-boundary units' shared scan, nw_bq.h) and every face
+//                                           takes its root's rank: labels in order of the components' smallest face ids;
 //   k_ws_stats                              one thread per face, float64 terms turned into 64-bit fixed point and summed by wave when the
 //                                           wave's faces share a label (the usual case), by lane otherwise: integer sums, the same bytes
 //                                           on every run;
@@ -21,7 +21,6 @@
 // All stores are vector stores; no kernel uses scratch (build.py's KERNEL_BUDGETS checks it).
 #include <hip/hip_runtime.h>
 #include <cstdint>
-#include <cstring>
 #include <cmath>
 #include <cfloat>
 #include <climits>
@@ -30,10 +29,11 @@
 #include <algorithm>
 
 #include "../../include/nw_surgery.h"
+#include "nw_bq.h"
+#include "nw_device.h"
 
 #define NWS_EXPORT extern "C" __attribute__((visibility("default")))
 #define NWS_BLOCK 256
-#define NWS_SCAN_TILE 2048          // 256 threads x 8
 #define NWS_WQ 8                    // queries per k_ws_winding workgroup
 #define NWS_WF 4                    // faces per k_ws_winding thread
 
@@ -102,83 +102,7 @@ __global__ __launch_bounds__(NWS_BLOCK) void k_ws_number(int nf, const int *__re
     label[f] = r < 0 ? -1 : rank[r];
 }
 
-// ---- exclusive scan: out[0..n] with out[n] = total (as nw_holepunch.hip's k_hp_scan_*) --------------------------------------------
-__device__ __forceinline__ int ws_wave_incl_scan(int v, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-
-__global__ __launch_bounds__(NWS_BLOCK) void k_ws_scan_tiles(const int *__restrict__ in, int n, int *__restrict__ bsum)
-{
-    __shared__ int s_w[4];
-    const int base = blockIdx.x * NWS_SCAN_TILE + threadIdx.x * 8;
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s += (base + k < n) ? in[base + k] : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) bsum[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-
-__global__ __launch_bounds__(1024) void k_ws_scan_bsums(int *__restrict__ bsum, int nb)
-{
-    __shared__ int s_w[16];
-    __shared__ int s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int base = 0; base < nb; base += 1024) {
-        const int i = base + threadIdx.x;
-        const int v = i < nb ? bsum[i] : 0;
-        const int inc = ws_wave_incl_scan(v, lane);
-        if (lane == 63) s_w[wv] = inc;
-        __syncthreads();
-        int woff = 0;
-        for (int w = 0; w < wv; ++w) woff += s_w[w];
-        const int carry = s_carry;
-        if (i < nb) bsum[i] = carry + woff + inc - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = carry + woff + inc;
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(NWS_BLOCK) void k_ws_scan_final(const int *__restrict__ in, int n, const int *__restrict__ bsum, int *__restrict__ out)
-{
-    __shared__ int s_w[4];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int base = blockIdx.x * NWS_SCAN_TILE + threadIdx.x * 8;
-    int v[8];
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { v[k] = (base + k < n) ? in[base + k] : 0; s += v[k]; }
-    const int inc = ws_wave_incl_scan(s, lane);
-    if (lane == 63) s_w[wv] = inc;
-    __syncthreads();
-    int off = bsum[blockIdx.x] + inc - s;
-    for (int w = 0; w < wv; ++w) off += s_w[w];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        if (base + k < n) out[base + k] = off;
-        off += v[k];
-        if (base + k == n - 1) out[n] = off;
-    }
-}
-
 // ---- per-component statistics ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int ws_ord(float f)           // monotone float -> int map (atomicMin / atomicMax on floats)
-{
-    const int i = __float_as_int(f);
-    return i >= 0 ? i : i ^ 0x7fffffff;
-}
-
 __device__ __forceinline__ i64 ws_wave_sum(i64 v)
 {
 #pragma unroll
@@ -252,7 +176,7 @@ __global__ __launch_bounds__(NWS_BLOCK) void k_ws_stats(const float *__restrict_
         }
         const int ids[3] = {i0, i1, i2};
         for (int c = 0; c < 3; ++c)
-            for (int d = 0; d < 3; ++d) { const int o = ws_ord(pos[3 * ids[c] + d]); lo[d] = min(lo[d], o); hi[d] = max(hi[d], o); }
+            for (int d = 0; d < 3; ++d) { const int o = bq::enc_ord(pos[3 * ids[c] + d]); lo[d] = min(lo[d], o); hi[d] = max(hi[d], o); }
     }
     // one atomic per wave when every lane of the wave holds a face of the same component (lanes without a face join any wave)
     const int wl = ws_wave_label(lab);
@@ -281,8 +205,6 @@ __global__ __launch_bounds__(NWS_BLOCK) void k_ws_bbox_init(int *__restrict__ bb
 }
 
 // ---- winding numbers ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float ws_dec_ord(int v) { return __int_as_float(v >= 0 ? v : v ^ 0x7fffffff); }
-
 // active[q * C + c] = 1 if component c is evaluated for query q: not the query's own, and its box holds the point
 __global__ __launch_bounds__(NWS_BLOCK) void k_ws_active(const float *__restrict__ queries, const int *__restrict__ qcomp, int nq, int nc,
                                                          const int *__restrict__ bbox, unsigned char *__restrict__ active)
@@ -293,7 +215,7 @@ __global__ __launch_bounds__(NWS_BLOCK) void k_ws_active(const float *__restrict
     bool in = qcomp == nullptr || qcomp[q] != c;
     for (int d = 0; d < 3 && in; ++d) {
         const float x = queries[3 * q + d];
-        in = bbox[6 * c + d] != INT_MAX && x >= ws_dec_ord(bbox[6 * c + d]) && x <= ws_dec_ord(bbox[6 * c + 3 + d]);
+        in = bbox[6 * c + d] != INT_MAX && x >= bq::dec_ord(bbox[6 * c + d]) && x <= bq::dec_ord(bbox[6 * c + 3 + d]);
     }
     active[i] = in ? 1 : 0;
 }
@@ -409,7 +331,7 @@ __global__ __launch_bounds__(64) void k_ws_pick(int *__restrict__ hist, int shif
         const int *h = hist + ((t == 1 && p1 != p0) ? 256 : 0);
         int v[4], s = 0;
         for (int j = 0; j < 4; ++j) { v[j] = h[4 * lane + j]; s += v[j]; }
-        const int inc = ws_wave_incl_scan(s, lane);
+        const int inc = nw_wave_incl_scan(s, lane);
         const int k = sel->k[t];
         int excl = inc - s, hit = -1, before = 0;
         for (int j = 0; j < 4; ++j) {
@@ -451,62 +373,23 @@ __global__ __launch_bounds__(NWS_BLOCK) void k_ws_flag(const float *__restrict__
 // =====================================================================================================================================
 // host side
 // =====================================================================================================================================
-namespace {
+using bq::DevBuf;
+using bq::fail;
+using bq::nblk;
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    hipError_t ensure(size_t b)
-    {
-        if (b <= bytes && p) return hipSuccess;
-        if (p) { (void)hipFree(p); p = nullptr; bytes = 0; }
-        const hipError_t e = hipMalloc(&p, std::max<size_t>(b, 256));
-        if (e == hipSuccess) bytes = std::max<size_t>(b, 256);
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-    template <class T> T *as() const { return (T *)p; }
-};
-
-}  // namespace
-
-struct nws_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
+struct nws_ctx : bq::Ctx {
     DevBuf pos, faces, twin, label, a, b, c, d, e, f;
 };
 
 namespace {
 
-int fail(nws_ctx *ctx, int code, const std::string &msg)
-{
-    if (ctx) ctx->err = msg;
-    return code;
-}
-
-#define NWS_HIP(call)                                                                                          \
-    do {                                                                                                       \
-        hipError_t e_ = (call);                                                                                \
-        if (e_ != hipSuccess)                                                                                  \
-            return fail(ctx, e_ == hipErrorOutOfMemory ? NWS_ERR_NOMEM : NWS_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+#define NWS_HIP(call) BQ_HIP(call, NWS_ERR_NOMEM, NWS_ERR_HIP)
 
 #define NWS_TRY(call)                                                                                          \
     do {                                                                                                       \
         const int r_ = (call);                                                                                 \
         if (r_ != NWS_OK) return r_;                                                                           \
     } while (0)
-
-inline int nblk(int64_t n, int b = NWS_BLOCK) { return (int)((n + b - 1) / b); }
-
-int check_faces(const int32_t *faces, int64_t nf, int64_t nv)
-{
-    if (!faces || nf < 1 || nf > (1ll << 29) || nv < 3 || nv > (1ll << 30)) return NWS_ERR_BADARG;
-    for (int64_t i = 0; i < 3 * nf; ++i)
-        if (faces[i] < 0 || faces[i] >= nv) return NWS_ERR_BADARG;
-    return NWS_OK;
-}
 
 int check_twin(const int32_t *twin, int64_t nf)
 {
@@ -524,33 +407,10 @@ int check_label(const int32_t *label, int64_t nf, int32_t nc)
     return NWS_OK;
 }
 
-int check_pos(const float *pos, int64_t nv, float *max_abs)
-{
-    if (!pos) return NWS_ERR_BADARG;
-    float m = 0.0f;
-    for (int64_t i = 0; i < 3 * nv; ++i) {
-        if (!std::isfinite(pos[i])) return NWS_ERR_BADARG;
-        m = std::max(m, std::fabs(pos[i]));
-    }
-    if (max_abs) *max_abs = m;
-    return NWS_OK;
-}
-
 template <class T> int upload(nws_ctx *ctx, DevBuf &buf, const T *src, int64_t n)
 {
     NWS_HIP(buf.ensure(sizeof(T) * (size_t)n));
     NWS_HIP(hipMemcpyAsync(buf.p, src, sizeof(T) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    return NWS_OK;
-}
-
-int scan_exclusive(nws_ctx *ctx, const int *in, int n, int *out, DevBuf &tmp)
-{
-    const int nb = (n + NWS_SCAN_TILE - 1) / NWS_SCAN_TILE;
-    NWS_HIP(tmp.ensure(sizeof(int) * (size_t)(nb + 1)));
-    hipLaunchKernelGGL(k_ws_scan_tiles, dim3(nb), dim3(NWS_BLOCK), 0, ctx->stream, in, n, tmp.as<int>());
-    hipLaunchKernelGGL(k_ws_scan_bsums, dim3(1), dim3(1024), 0, ctx->stream, tmp.as<int>(), nb);
-    hipLaunchKernelGGL(k_ws_scan_final, dim3(nb), dim3(NWS_BLOCK), 0, ctx->stream, in, n, tmp.as<int>(), out);
-    NWS_HIP(hipGetLastError());
     return NWS_OK;
 }
 
@@ -579,8 +439,6 @@ ws_frame make_frame(const float *pos, int64_t nv, int nf)
     return fr;
 }
 
-float dec_ord(int v) { const int i = v >= 0 ? v : v ^ 0x7fffffff; float f; std::memcpy(&f, &i, 4); return f; }
-
 // the accumulators of k_ws_stats into the ctx's buffers c (u64: count, area, volume, border, C each, then the 3C normal sums) and d (bbox,
 // 6C ordered ints); pos, faces, twin and label are on the device already
 int run_stats(nws_ctx *ctx, int nf, int nc, const ws_frame &fr)
@@ -603,33 +461,11 @@ int run_stats(nws_ctx *ctx, int nf, int nc, const ws_frame &fr)
 
 NWS_EXPORT int nws_abi_version(void) { return NWS_ABI_VERSION; }
 
-NWS_EXPORT int nws_create(int device, nws_ctx **out)
-{
-    if (!out || device < 0) return NWS_ERR_BADARG;
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return NWS_ERR_HIP;
-    if (device >= ndev) return NWS_ERR_BADARG;
-    if (hipSetDevice(device) != hipSuccess) return NWS_ERR_HIP;
-    nws_ctx *ctx = new nws_ctx();
-    ctx->device = device;
-    if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { delete ctx; return NWS_ERR_HIP; }
-    *out = ctx;
-    return NWS_OK;
-}
+NWS_EXPORT int nws_create(int device, nws_ctx **out) { return bq::create(device, out, NWS_ERR_BADARG, NWS_ERR_HIP); }
 
-NWS_EXPORT void nws_destroy(nws_ctx *ctx)
-{
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    DevBuf *bufs[] = {&ctx->pos, &ctx->faces, &ctx->twin, &ctx->label, &ctx->a, &ctx->b, &ctx->c, &ctx->d, &ctx->e, &ctx->f};
-    for (DevBuf *b : bufs) b->release();
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
-}
+NWS_EXPORT void nws_destroy(nws_ctx *ctx) { bq::destroy(ctx); }
 
-NWS_EXPORT const char *nws_last_error(nws_ctx *ctx) { return ctx ? ctx->err.c_str() : "null ctx"; }
+NWS_EXPORT const char *nws_last_error(nws_ctx *ctx) { return bq::last_error(ctx); }
 
 NWS_EXPORT int nws_label_faces(nws_ctx *ctx, const int32_t *faces, const int32_t *twin, const uint8_t *mask, int64_t n_faces, int32_t *label_out,
                                int32_t *n_components_out)
@@ -654,7 +490,7 @@ NWS_EXPORT int nws_label_faces(nws_ctx *ctx, const int32_t *faces, const int32_t
     hipLaunchKernelGGL(k_ws_hook, dim3(nblk(nf)), dim3(NWS_BLOCK), 0, ctx->stream, ctx->twin.as<int>(), nf, parent);
     hipLaunchKernelGGL(k_ws_compress, dim3(nblk(nf)), dim3(NWS_BLOCK), 0, ctx->stream, nf, parent, label, is_root);
     NWS_HIP(hipGetLastError());
-    NWS_TRY(scan_exclusive(ctx, is_root, nf, rank, ctx->e));
+    NWS_HIP(bq::scan_exclusive(ctx->stream, is_root, nf, rank, ctx->e));
     hipLaunchKernelGGL(k_ws_number, dim3(nblk(nf)), dim3(NWS_BLOCK), 0, ctx->stream, nf, rank, label);
     NWS_HIP(hipGetLastError());
     int nc = 0;
@@ -670,8 +506,7 @@ NWS_EXPORT int nws_component_stats(nws_ctx *ctx, const float *pos, int64_t n_ver
                                    int64_t *n_border)
 {
     if (n_components < 0 || n_components > (1 << 28)) return NWS_ERR_BADARG;
-    NWS_TRY(check_faces(faces, n_faces, n_vertices));
-    NWS_TRY(check_pos(pos, n_vertices, nullptr));
+    if (!bq::mesh_ok(pos, n_vertices, faces, n_faces)) return NWS_ERR_BADARG;
     NWS_TRY(check_twin(twin, n_faces));
     NWS_TRY(check_label(label, n_faces, n_components));
     if (!ctx) return NWS_ERR_BADARG;
@@ -702,7 +537,7 @@ NWS_EXPORT int nws_component_stats(nws_ctx *ctx, const float *pos, int64_t n_ver
         if (bbox)
             for (int d = 0; d < 6; ++d) {
                 const int o = bb[6 * (size_t)c + d];
-                bbox[6 * (size_t)c + d] = (o == INT_MAX) ? FLT_MAX : (o == INT_MIN) ? -FLT_MAX : dec_ord(o);
+                bbox[6 * (size_t)c + d] = (o == INT_MAX) ? FLT_MAX : (o == INT_MIN) ? -FLT_MAX : bq::dec_ord(o);
             }
     }
     return NWS_OK;
@@ -714,8 +549,7 @@ NWS_EXPORT int nws_winding(nws_ctx *ctx, const float *pos, int64_t n_vertices, c
     if (!queries || !w_out || n_queries < 0 || n_queries > (1 << 24) || n_components < 0 || n_components > (1 << 24) ||
         n_queries * (int64_t)n_components > (1ll << 28))
         return NWS_ERR_BADARG;
-    NWS_TRY(check_faces(faces, n_faces, n_vertices));
-    NWS_TRY(check_pos(pos, n_vertices, nullptr));
+    if (!bq::mesh_ok(pos, n_vertices, faces, n_faces)) return NWS_ERR_BADARG;
     NWS_TRY(check_label(label, n_faces, n_components));
     for (int64_t i = 0; i < 3 * n_queries; ++i)
         if (!std::isfinite(queries[i])) return NWS_ERR_BADARG;
@@ -761,8 +595,7 @@ NWS_EXPORT int nws_short_edge_vertices(nws_ctx *ctx, const float *pos, int64_t n
                                        uint8_t *flag_out, float *median_out)
 {
     if (!flag_out || !(threshold >= 0.0f) || !std::isfinite(threshold)) return NWS_ERR_BADARG;
-    NWS_TRY(check_faces(faces, n_faces, n_vertices));
-    NWS_TRY(check_pos(pos, n_vertices, nullptr));
+    if (!bq::mesh_ok(pos, n_vertices, faces, n_faces)) return NWS_ERR_BADARG;
     if (!ctx) return NWS_ERR_BADARG;
     NWS_HIP(hipSetDevice(ctx->device));
     const int nh = (int)(3 * n_faces);

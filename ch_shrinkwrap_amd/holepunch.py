@@ -32,64 +32,38 @@ _L = None
 
 
 def load():
-    """The library's nwh_ entry points (the same .so as include/nanowrap.h's; loaded through _lib so that the HIP runtime order holds)."""
+    """The library's nwh_ entry points."""
     global _L
-    if _L is not None:
-        return _L
-    _lib.load()
-    L = ctypes.CDLL(_lib.LIB_PATH)           # (own function objects: argtypes here do not touch _lib's)
-    for s in SYMBOLS:
-        if not hasattr(L, s):
-            raise RuntimeError('%s does not export %s: rebuild it (python -m ch_shrinkwrap_amd.build)' % (_lib.LIB_PATH, s))
-    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
-    L.nwh_abi_version.argtypes = []
-    L.nwh_create.argtypes = [i32, ctypes.POINTER(vp)]
-    L.nwh_destroy.argtypes = [vp]
-    L.nwh_destroy.restype = None
-    L.nwh_last_error.argtypes = [vp]
-    L.nwh_last_error.restype = ctypes.c_char_p
-    L.nwh_set_points.argtypes = [vp, vp, i64, f32]
-    L.nwh_empty_faces.argtypes = [vp, vp, i64, vp, i64, f32, vp, vp]
-    L.nwh_pair_faces.argtypes = [vp, vp, i64, vp, i64, vp, vp, i64, vp]
-    L.nwh_prism_empty.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, i64, f32, vp]
-    if L.nwh_abi_version() != ABI_VERSION:
-        raise RuntimeError('nw_holepunch ABI %d, expected %d: rebuild the library' % (L.nwh_abi_version(), ABI_VERSION))
-    _L = L
-    return L
+    if _L is None:
+        vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
+        _L = _lib.load_entry_points(SYMBOLS, {
+            'nwh_abi_version': [], 'nwh_create': [i32, ctypes.POINTER(vp)], 'nwh_destroy': [vp], 'nwh_last_error': [vp],
+            'nwh_set_points': [vp, vp, i64, f32],
+            'nwh_empty_faces': [vp, vp, i64, vp, i64, f32, vp, vp],
+            'nwh_pair_faces': [vp, vp, i64, vp, i64, vp, vp, i64, vp],
+            'nwh_prism_empty': [vp, vp, i64, vp, i64, vp, vp, vp, i64, f32, vp]}, 'nwh_abi_version', ABI_VERSION, 'nw_holepunch')
+    return _L
 
 
-def _p(a):
-    return None if a is None else a.ctypes.data
+_p, _mesh = _lib.ptr, _lib.mesh_arrays
 
 
-class HolePunchContext(object):
+class HolePunchContext(_lib.QueryContext):
     """One nwh_ctx: the cell grid of a fit's localizations (set once: they do not move) and the three point queries."""
+    prefix, errors, gpu_only, load = 'nwh_', ERRORS, 'hole punching runs', staticmethod(load)
 
     def __init__(self, device=0):
-        self.L = load()
-        self.h = ctypes.c_void_p()
-        code = self.L.nwh_create(int(device), ctypes.byref(self.h))
-        if code != NWH_OK:
-            raise RuntimeError('nwh_create failed: %s -- hole punching runs on the GPU only' % ERRORS.get(code, code))
+        _lib.QueryContext.__init__(self, device)
         self.n_points = 0
-
-    def check(self, code, what):
-        if code != NWH_OK:
-            msg = self.L.nwh_last_error(self.h) if self.h else b''
-            raise RuntimeError('%s: %s %s' % (what, ERRORS.get(code, 'error %d' % code), (msg or b'').decode()))
 
     def set_points(self, points, cell_size=0.0):
         pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
         self.check(self.L.nwh_set_points(self.h, _p(pts), pts.shape[0], float(cell_size)), 'nwh_set_points')
         self.n_points = pts.shape[0]
 
-    @staticmethod
-    def _mesh(pos, faces):
-        return np.ascontiguousarray(pos, np.float32).reshape(-1, 3), np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
-
     def empty_faces(self, pos, faces, eps, return_dist=False):
         """(F,) bool: no localization within eps of the face centroid (and the nearest distance clipped at eps)."""
-        pos, faces = self._mesh(pos, faces)
+        pos, faces = _mesh(pos, faces)
         far = np.empty(faces.shape[0], np.uint8)
         dist = np.empty(faces.shape[0], np.float32) if return_dist else None
         self.check(self.L.nwh_empty_faces(self.h, _p(pos), pos.shape[0], _p(faces), faces.shape[0], float(eps), _p(far), _p(dist)), 'nwh_empty_faces')
@@ -97,7 +71,7 @@ class HolePunchContext(object):
 
     def pair_faces(self, pos, faces, face_normals, cands):
         """(C,) int32: the raw `pairs` array of c_holepunch_pair_candidate_faces (index into cands, or -1)."""
-        pos, faces = self._mesh(pos, faces)
+        pos, faces = _mesh(pos, faces)
         fn = np.ascontiguousarray(face_normals, np.float32).reshape(-1, 3)
         cands = np.ascontiguousarray(cands, np.int32)
         pairs = np.full(cands.shape[0], -1, np.int32)
@@ -109,7 +83,7 @@ class HolePunchContext(object):
 
     def prism_empty(self, pos, faces, face_normals, cands, pair_idx, eps):
         """(C,) bool: the prism between candidate k and candidate pair_idx[k] holds no localization."""
-        pos, faces = self._mesh(pos, faces)
+        pos, faces = _mesh(pos, faces)
         fn = np.ascontiguousarray(face_normals, np.float32).reshape(-1, 3)
         cands = np.ascontiguousarray(cands, np.int32)
         pair_idx = np.ascontiguousarray(pair_idx, np.int32)
@@ -121,17 +95,6 @@ class HolePunchContext(object):
         self.check(self.L.nwh_prism_empty(self.h, _p(pos), pos.shape[0], _p(faces), faces.shape[0], _p(fn), _p(cands), _p(pair_idx),
                                           cands.shape[0], float(eps), _p(out)), 'nwh_prism_empty')
         return out.astype(bool)
-
-    def close(self):
-        if self.h:
-            self.L.nwh_destroy(self.h)
-            self.h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---- host steps -------------------------------------------------------------------------------------------------------------------

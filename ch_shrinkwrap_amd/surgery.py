@@ -33,54 +33,25 @@ _L = None
 
 
 def load():
-    """The library's nws_ entry points (the same .so as include/nanowrap.h's; loaded through _lib so that the HIP runtime order holds)."""
+    """The library's nws_ entry points."""
     global _L
-    if _L is not None:
-        return _L
-    _lib.load()
-    L = ctypes.CDLL(_lib.LIB_PATH)           # (own function objects: argtypes here do not touch _lib's)
-    for s in SYMBOLS:
-        if not hasattr(L, s):
-            raise RuntimeError('%s does not export %s: rebuild it (python -m ch_shrinkwrap_amd.build)' % (_lib.LIB_PATH, s))
-    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
-    L.nws_abi_version.argtypes = []
-    L.nws_create.argtypes = [i32, ctypes.POINTER(vp)]
-    L.nws_destroy.argtypes = [vp]
-    L.nws_destroy.restype = None
-    L.nws_last_error.argtypes = [vp]
-    L.nws_last_error.restype = ctypes.c_char_p
-    L.nws_label_faces.argtypes = [vp, vp, vp, vp, i64, vp, vp]
-    L.nws_component_stats.argtypes = [vp, vp, i64, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp]
-    L.nws_winding.argtypes = [vp, vp, i64, vp, vp, i64, i32, vp, vp, i64, vp]
-    L.nws_short_edge_vertices.argtypes = [vp, vp, i64, vp, i64, f32, vp, vp]
-    if L.nws_abi_version() != ABI_VERSION:
-        raise RuntimeError('nw_surgery ABI %d, expected %d: rebuild the library' % (L.nws_abi_version(), ABI_VERSION))
-    _L = L
-    return L
+    if _L is None:
+        vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
+        _L = _lib.load_entry_points(SYMBOLS, {
+            'nws_abi_version': [], 'nws_create': [i32, ctypes.POINTER(vp)], 'nws_destroy': [vp], 'nws_last_error': [vp],
+            'nws_label_faces': [vp, vp, vp, vp, i64, vp, vp],
+            'nws_component_stats': [vp, vp, i64, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp],
+            'nws_winding': [vp, vp, i64, vp, vp, i64, i32, vp, vp, i64, vp],
+            'nws_short_edge_vertices': [vp, vp, i64, vp, i64, f32, vp, vp]}, 'nws_abi_version', ABI_VERSION, 'nw_surgery')
+    return _L
 
 
-def _p(a):
-    return None if a is None else a.ctypes.data
+_p, _mesh = _lib.ptr, _lib.mesh_arrays
 
 
-def _mesh(pos, faces):
-    return np.ascontiguousarray(pos, np.float32).reshape(-1, 3), np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
-
-
-class SurgeryContext(object):
+class SurgeryContext(_lib.QueryContext):
     """One nws_ctx: the four mesh-wide queries of the block-boundary surgery on one device."""
-
-    def __init__(self, device=0):
-        self.L = load()
-        self.h = ctypes.c_void_p()
-        code = self.L.nws_create(int(device), ctypes.byref(self.h))
-        if code != NWS_OK:
-            raise RuntimeError('nws_create failed: %s -- neck removal and short-edge cleanup run on the GPU only' % ERRORS.get(code, code))
-
-    def check(self, code, what):
-        if code != NWS_OK:
-            msg = self.L.nws_last_error(self.h) if self.h else b''
-            raise RuntimeError('%s: %s %s' % (what, ERRORS.get(code, 'error %d' % code), (msg or b'').decode()))
+    prefix, errors, gpu_only, load = 'nws_', ERRORS, 'neck removal and short-edge cleanup run', staticmethod(load)
 
     def label_faces(self, faces, twin, mask=None):
         """(label (F,) int32, number of components): edge-connected components of the faces with mask != 0, numbered in order of their
@@ -130,17 +101,6 @@ class SurgeryContext(object):
         self.check(self.L.nws_short_edge_vertices(self.h, _p(pos), pos.shape[0], _p(faces), faces.shape[0], float(threshold), _p(flag), _p(med)),
                    'nws_short_edge_vertices')
         return flag.astype(bool), med[0]
-
-    def close(self):
-        if self.h:
-            self.L.nws_destroy(self.h)
-            self.h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---- labelling and adjacency on the host ------------------------------------------------------------------------------------------
