@@ -32,6 +32,7 @@ _QUERY = _BASE + ['-ffp-contract=off', '-Wall', '-Wno-unused-function']
 _BQ = [_csrc('nw_bq.h'), _csrc('nw_device.h')]            # (nw_device.h: nw_wave_incl_scan)
 
 OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_BQ = _csrc('nanowrap.o'), _csrc('nw_holepunch.o'), _csrc('nw_surgery.o'), _csrc('nw_bq.o')
+OBJ_ISOSURFACE = _csrc('nw_isosurface.o')
 # the translation units of libnanowrap_hip.so: (source, object, what else it is rebuilt for, flags).  The objects are linked in this order.
 UNITS = [
     # the per-iteration kernels and the C-ABI; every header of csrc/ but nw_bq.h is included by it (directly or through nw_kernels.h)
@@ -46,7 +47,9 @@ UNITS = [
     (_csrc('nw_holepunch.hip'), OBJ_HOLEPUNCH, [_include('nw_holepunch.h'), _csrc('nw_bq.h')], _QUERY),
     # the neck / short-edge / inner-surface queries
     (_csrc('nw_surgery.hip'), OBJ_SURGERY, [_include('nw_surgery.h')] + _BQ, _QUERY),
-    # what the two above share (csrc/nw_bq.h): the exclusive scan
+    # the density isosurface of the cloud (the start surface of a fit)
+    (_csrc('nw_isosurface.hip'), OBJ_ISOSURFACE, [_include('nw_isosurface.h'), _csrc('nw_bq.h')], _QUERY),
+    # what the three above share (csrc/nw_bq.h): the exclusive scan
     (_csrc('nw_bq.hip'), OBJ_BQ, _BQ, _QUERY),
 ]
 DEPS = sorted(set(d for src, _, extra, _ in UNITS for d in [src] + extra))
@@ -117,12 +120,22 @@ KERNEL_BUDGETS = {
     'k_ws_hist':                      (16, 2048),          # two 256-bin histograms
     'k_ws_pick':                      (32, 0),
     'k_ws_flag':                      (16, 0),
-    # the exclusive scan both share (csrc/nw_bq.o)
+    # the density isosurface (csrc/nw_isosurface.o): set-up kernels, budgeted for zero scratch and against silent growth
+    'k_iso_count':                    (16, 16 * 1024),     # the LDS table of voxel ids and counts: 2048 slots of 8 bytes
+    'k_iso_widen':                    (16, 0),
+    'k_iso_smooth':                   (16, 0),
+    'k_iso_hist':                     (16, 1024),          # one 256-bin histogram
+    'k_iso_pattern':                  (32, 0),
+    'k_iso_compact':                  (16, 0),
+    'k_iso_cell_counts':              (16, 0),
+    'k_iso_vertices':                 (64, 0),
+    'k_iso_quads':                    (32, 0),
+    # the exclusive scan they share (csrc/nw_bq.o)
     'k_bq_scan_tiles':                (32, 1024),
     'k_bq_scan_bsums':                (32, 1024),
     'k_bq_scan_final':                (32, 1024),
 }
-BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_BQ]
+BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_BQ]
 
 
 def kernel_resources(obj=None):
