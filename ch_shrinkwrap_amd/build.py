@@ -33,6 +33,7 @@ _BQ = [_csrc('nw_bq.h'), _csrc('nw_device.h')]            # (nw_device.h: nw_wav
 
 OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_BQ = _csrc('nanowrap.o'), _csrc('nw_holepunch.o'), _csrc('nw_surgery.o'), _csrc('nw_bq.o')
 OBJ_ISOSURFACE = _csrc('nw_isosurface.o')
+OBJ_EVALUATION = _csrc('nw_evaluation.o')
 # the translation units of libnanowrap_hip.so: (source, object, what else it is rebuilt for, flags).  The objects are linked in this order.
 UNITS = [
     # the per-iteration kernels and the C-ABI; every header of csrc/ but nw_bq.h is included by it (directly or through nw_kernels.h)
@@ -49,7 +50,10 @@ UNITS = [
     (_csrc('nw_surgery.hip'), OBJ_SURGERY, [_include('nw_surgery.h')] + _BQ, _QUERY),
     # the density isosurface of the cloud (the start surface of a fit)
     (_csrc('nw_isosurface.hip'), OBJ_ISOSURFACE, [_include('nw_isosurface.h'), _csrc('nw_bq.h')], _QUERY),
-    # what the three above share (csrc/nw_bq.h): the exclusive scan
+    # the fit-quality metric: mesh sampling and nearest neighbours between two clouds (nw_evaluation_core.h: the sampler's arithmetic,
+    # which the tests also compile for the CPU)
+    (_csrc('nw_evaluation.hip'), OBJ_EVALUATION, [_include('nw_evaluation.h'), _csrc('nw_bq.h'), _csrc('nw_evaluation_core.h')], _QUERY),
+    # what the four above share (csrc/nw_bq.h): the exclusive scan
     (_csrc('nw_bq.hip'), OBJ_BQ, _BQ, _QUERY),
 ]
 DEPS = sorted(set(d for src, _, extra, _ in UNITS for d in [src] + extra))
@@ -130,12 +134,21 @@ KERNEL_BUDGETS = {
     'k_iso_cell_counts':              (16, 0),
     'k_iso_vertices':                 (64, 0),
     'k_iso_quads':                    (32, 0),
+    # the fit-quality metric (csrc/nw_evaluation.o): end-of-fit queries, budgeted for zero scratch and against silent growth
+    'k_ev_face_setup':                (64, 0),             # the float32 set-up of a face: 23 values live until they are stored
+    'k_ev_node_test':                 (32, 0),
+    'k_ev_emit':                      (32, 0),
+    'k_ev_bbox':                      (48, 0),             # six 64-bit keys per thread
+    'k_ev_cell_count':                (48, 0),
+    'k_ev_scatter':                   (16, 0),
+    'k_ev_nearest':                   (64, 64),            # float64 query, best pair and the ring walk's bounds: 8 waves per SIMD; LDS = the four waves' sums
+    'k_ev_sum_final':                 (16, 64),
     # the exclusive scan they share (csrc/nw_bq.o)
     'k_bq_scan_tiles':                (32, 1024),
     'k_bq_scan_bsums':                (32, 1024),
     'k_bq_scan_final':                (32, 1024),
 }
-BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_BQ]
+BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_BQ]
 
 
 def kernel_resources(obj=None):

@@ -465,6 +465,51 @@ class TriMesh(object):
     def area(self):
         return float(self._faces['area'].sum())
 
+    # -- what upstream's MeshProperties module reads (evaluation.mesh_properties has the definitions).  None of them is a stored field:
+    # each is computed from the face array when it is asked for and kept until the face array is replaced (a TriMesh's topology is
+    # fixed: a remesher makes a new TriMesh).  euler and manifold are host work (twins and two connected-components passes, O(faces));
+    # components and genus label the faces on the device (one SurgeryContext, one upload) and raise RuntimeError without a GPU.
+    def _topology_cached(self, key, compute):
+        cache = self.__dict__.get('_topology_cache')
+        if cache is None or cache[0] is not self._faces_arr:
+            cache = (self._faces_arr, {})
+            self.__dict__['_topology_cache'] = cache
+        if key not in cache[1]:
+            cache[1].update(compute())
+        return cache[1][key]
+
+    def _host_topology(self):
+        from .evaluation import mesh_topology
+        top = mesh_topology(self._faces_arr, self._position_records().shape[0])
+        return dict(euler=int(top['euler']), manifold=top['manifold'])
+
+    def _device_topology(self):
+        from .evaluation import mesh_properties
+        q = mesh_properties(self)
+        return dict(components=q['components'], genus=q['genus'], euler=q['euler'], manifold=q['manifold'])
+
+    @property
+    def euler(self):
+        """V - E + F (host; cached per face array)."""
+        return self._topology_cached('euler', self._host_topology)
+
+    euler_characteristic = euler
+
+    @property
+    def manifold(self):
+        """No directed edge twice and one fan of faces at every vertex (host; cached per face array)."""
+        return self._topology_cached('manifold', self._host_topology)
+
+    @property
+    def components(self):
+        """The number of edge-connected components, labelled on the device (cached per face array; no host fallback: raises without a GPU)."""
+        return self._topology_cached('components', self._device_topology)
+
+    @property
+    def genus(self):
+        """The sum of the components' genera (needs `components`: on the device, cached per face array, raises without a GPU)."""
+        return self._topology_cached('genus', self._device_topology)
+
     def neighbor_vertex_table(self):
         """(M, NEIGHBORSIZE) i4 table of 1-ring VERTEX ids, -1 padded -- what the reference caches
         at mesh_conj_grad.py:50-54."""

@@ -1,7 +1,9 @@
 """
 End-to-end example from the localizations alone: the start surface is made from the cloud, not handed in.
 
-    python examples/fit_from_cloud.py [scale]       (scale 0.1 = 500 000 localizations, default; 1.0 = 5 000 000)
+    python examples/fit_from_cloud.py [scale] [host | device]
+        (scale 0.1 = 500 000 localizations, default; 1.0 = 5 000 000; the second argument is where the fit is scored:
+        evaluation.fit_quality's backend, default host)
 
 Upstream's recipe (ch_shrinkwrap/test_evaluation_recipe.yaml:25-38 in the reference) is Octree -> DualMarchingCubes -> ShrinkwrapMembrane;
 here `DensitySurface` stands in for the first two (a regular-grid density isosurface on the GPU: it is not PYME's algorithm, see
@@ -20,7 +22,7 @@ from ch_shrinkwrap_amd.membrane_mesh import ShrinkwrapMembrane     # noqa: E402
 from ch_shrinkwrap_amd.surgery import euler_characteristic        # noqa: E402
 
 
-def main(scale=0.1):
+def main(scale=0.1, score_backend='host'):
     cfg = synth.make_config('c4', scale=scale, seed=0)
     pts = cfg['points']
     table = {'x': pts[:, 0], 'y': pts[:, 1], 'z': pts[:, 2],
@@ -38,11 +40,11 @@ def main(scale=0.1):
     t0 = time.time()
     mesh = ShrinkwrapMembrane(max_iters=39, remesh_frequency=5, curvature_weight=20.0, minimum_edge_length=max(5.0, 2.5 / np.sqrt(scale))).execute(ns)
     dt = time.time() - t0
-    q = fit_quality(mesh, synth.truth_cloud(cfg))
+    q = fit_quality(mesh, synth.truth_cloud(cfg), backend=score_backend)
     print('fitted mesh %d vertices / %d faces in %.2f s, genus %d, mse_rms against the true surface %.2f nm'
           % (mesh.vertices.shape[0], mesh.faces.shape[0], dt, (2 - euler_characteristic(mesh.faces)) // 2, q['mse_rms']))
     return surf, mesh, q
 
 
 if __name__ == '__main__':
-    main(float(sys.argv[1]) if len(sys.argv) > 1 else 0.1)
+    main(float(sys.argv[1]) if len(sys.argv) > 1 else 0.1, sys.argv[2] if len(sys.argv) > 2 else 'host')
