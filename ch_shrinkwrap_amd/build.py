@@ -34,6 +34,7 @@ _BQ = [_csrc('nw_bq.h'), _csrc('nw_device.h')]            # (nw_device.h: nw_wav
 OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_BQ = _csrc('nanowrap.o'), _csrc('nw_holepunch.o'), _csrc('nw_surgery.o'), _csrc('nw_bq.o')
 OBJ_ISOSURFACE = _csrc('nw_isosurface.o')
 OBJ_EVALUATION = _csrc('nw_evaluation.o')
+OBJ_SIMULATION = _csrc('nw_simulation.o')
 # the translation units of libnanowrap_hip.so: (source, object, what else it is rebuilt for, flags).  The objects are linked in this order.
 UNITS = [
     # the per-iteration kernels and the C-ABI; every header of csrc/ but nw_bq.h is included by it (directly or through nw_kernels.h)
@@ -53,7 +54,9 @@ UNITS = [
     # the fit-quality metric: mesh sampling and nearest neighbours between two clouds (nw_evaluation_core.h: the sampler's arithmetic,
     # which the tests also compile for the CPU)
     (_csrc('nw_evaluation.hip'), OBJ_EVALUATION, [_include('nw_evaluation.h'), _csrc('nw_bq.h'), _csrc('nw_evaluation_core.h')], _QUERY),
-    # what the four above share (csrc/nw_bq.h): the exclusive scan
+    # the SMLM cloud simulator: a shape's signed distance as a postfix program, the surface lattice, the localization model
+    (_csrc('nw_simulation.hip'), OBJ_SIMULATION, [_include('nw_simulation.h'), _csrc('nw_bq.h')], _QUERY),
+    # what the five above share (csrc/nw_bq.h): the exclusive scan
     (_csrc('nw_bq.hip'), OBJ_BQ, _BQ, _QUERY),
 ]
 DEPS = sorted(set(d for src, _, extra, _ in UNITS for d in [src] + extra))
@@ -143,12 +146,28 @@ KERNEL_BUDGETS = {
     'k_ev_scatter':                   (16, 0),
     'k_ev_nearest':                   (64, 64),            # float64 query, best pair and the ring walk's bounds: 8 waves per SIMD; LDS = the four waves' sums
     'k_ev_sum_final':                 (16, 64),
+    # the SMLM cloud simulator (csrc/nw_simulation.o): set-up kernels in float64, budgeted for zero scratch (the interpreter's value stack
+    # must stay in registers) and against silent growth
+    'k_sim_eval':                     (64, 0),             # the interpreter: eight float64 stack slots, the point and the frame: 8 waves per SIMD
+    'k_sim_normals':                  (72, 0),
+    'k_sim_cell_test':                (64, 0),
+    'k_sim_cell_split':               (24, 0),
+    'k_sim_leaf_test':                (64, 0),
+    'k_sim_leaf_emit':                (32, 0),
+    'k_sim_project':                  (72, 0),             # the interpreter seven times a step, the point and the gradient live across them: 7 waves per SIMD
+    'k_sim_loc_error':                (32, 0),
+    'k_sim_displace':                 (56, 0),             # float64 log and cospi
+    'k_sim_background':               (16, 0),
+    'k_sim_copy_hist':                (16, 1024),          # one 256-bin histogram
+    'k_sim_copy_equal':               (16, 0),
+    'k_sim_copy_keep':                (16, 0),
+    'k_sim_copy_emit':                (88, 0),             # three normals and three photon draws per copy, unrolled: 5 waves per SIMD
     # the exclusive scan they share (csrc/nw_bq.o)
     'k_bq_scan_tiles':                (32, 1024),
     'k_bq_scan_bsums':                (32, 1024),
     'k_bq_scan_final':                (32, 1024),
 }
-BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_BQ]
+BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_BQ]
 
 
 def kernel_resources(obj=None):
