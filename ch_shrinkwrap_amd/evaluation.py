@@ -177,8 +177,9 @@ def _sample_normals(mesh, d, ctx):
     return fn[face]
 
 
-def _points_from_mesh_host(mesh, dx_min):
-    """points_from_mesh with p = 1 on the host: the definition the kernels follow operation for operation."""
+def _face_grids(mesh, dx_min):
+    """The float32 set-up of points_from_mesh for every face of non-zero area: its in-plane frame, the slopes of its edges and its
+    grid (first node xa, ya relative to corner 0; nx x ny nodes).  -> a dict of arrays over those faces, and `ok`, which faces they are."""
     tris = np.asarray(mesh._vertices['position'])[np.asarray(mesh.faces)]                       # (F, 3, 3)
     norms = np.cross(tris[:, 2, :] - tris[:, 1, :], tris[:, 0, :] - tris[:, 1, :])               # :56
     nn = np.linalg.norm(norms, axis=1)
@@ -207,6 +208,24 @@ def _points_from_mesh_host(mesh, dx_min):
     ya, yb = yl - y0 - dx_min / 2, yu - y0
     nx = np.maximum(np.ceil((xb - xa) / dx_min), 0).astype(np.int64)                            # numpy.arange's length
     ny = np.maximum(np.ceil((yb - ya) / dx_min), 0).astype(np.int64)
+    return dict(ok=ok, tris=tris, e0=e0, e1=e1, x0=x0, y0=y0, x1=x1, y1=y1, x2=x2, y2=y2, m0=m0, m1=m1, m2=m2, s1=s1, s2=s2, xa=xa, ya=ya,
+                nx=nx, ny=ny)
+
+
+def node_counts(mesh, dx_min=5.0):
+    """(F,) int64: the grid nodes points_from_mesh lays over each face before it tests them against the triangle; 0 for a face of zero
+    area.  A face of non-zero area has at least one: its grid starts dx_min / 2 before the triangle's lower corner on both axes."""
+    g = _face_grids(mesh, dx_min)
+    per = np.zeros(g['ok'].shape[0], np.int64)
+    per[g['ok']] = g['nx'] * g['ny']
+    return per
+
+
+def _points_from_mesh_host(mesh, dx_min):
+    """points_from_mesh with p = 1 on the host: the definition the kernels follow operation for operation."""
+    g = _face_grids(mesh, dx_min)
+    tris, e0, e1, x0, y0, x1, y1, x2, y2 = (g[k] for k in ('tris', 'e0', 'e1', 'x0', 'y0', 'x1', 'y1', 'x2', 'y2'))
+    m0, m1, m2, s1, s2, xa, ya, nx, ny = (g[k] for k in ('m0', 'm1', 'm2', 's1', 's2', 'xa', 'ya', 'nx', 'ny'))
     per = nx * ny
     tot = int(per.sum())
     if tot == 0:

@@ -62,23 +62,30 @@ def ctx():
     c.close()
 
 
+def check_samples(ctx, v, f, dx):
+    """the device's samples of one mesh at one spacing against the host function's -> (samples, face ids)"""
+    mesh = Duck(v, f)
+    host = E.points_from_mesh(mesh, dx_min=dx)
+    n = ctx.sample_mesh(v, f, dx)
+    dev, face = ctx.samples(return_faces=True)
+    assert n == host.shape[0] and dev.dtype == np.float64 and dev.shape == host.shape
+    assert np.array_equal(_bits(dev), _bits(host))
+    assert face.dtype == np.int32 and (np.diff(face) >= 0).all() and face.min() >= 0 and face.max() < len(f)
+    # each sample lies in the plane of the face it names (float32 corners: a few ulp of the coordinates)
+    p0 = np.asarray(v, np.float64)[np.asarray(f)[face, 0]]
+    nrm = np.cross(np.asarray(v, np.float64)[np.asarray(f)[face, 1]] - p0, np.asarray(v, np.float64)[np.asarray(f)[face, 2]] - p0)
+    nrm /= np.linalg.norm(nrm, axis=1)[:, None]
+    assert np.abs(((dev - p0) * nrm).sum(1)).max() < 1e-4 * max(1.0, np.abs(v).max())
+    assert np.array_equal(_bits(E.points_from_mesh(mesh, dx_min=dx, backend='device', context=ctx)), _bits(host))
+    return dev, face
+
+
 @pytest.mark.parametrize('name', ['fit_quality', 'evaluation_case', 'off_origin', 'zero_area', 'remeshed_c2'])
 def test_samples_equal_the_host_function_bit_for_bit_and_in_order(ctx, name):
     v, f, spacings = sampling_case(name)
-    mesh = Duck(v, f)
     for dx in spacings:
-        host = E.points_from_mesh(mesh, dx_min=dx)
-        n = ctx.sample_mesh(v, f, dx)
-        dev, face = ctx.samples(return_faces=True)
-        assert n == host.shape[0] and dev.dtype == np.float64 and dev.shape == host.shape and n > 100
-        assert np.array_equal(_bits(dev), _bits(host))
-        assert face.dtype == np.int32 and (np.diff(face) >= 0).all() and face.min() >= 0 and face.max() < len(f)
-        # each sample lies in the plane of the face it names (float32 corners: a few ulp of the coordinates)
-        p0 = np.asarray(v, np.float64)[np.asarray(f)[face, 0]]
-        nrm = np.cross(np.asarray(v, np.float64)[np.asarray(f)[face, 1]] - p0, np.asarray(v, np.float64)[np.asarray(f)[face, 2]] - p0)
-        nrm /= np.linalg.norm(nrm, axis=1)[:, None]
-        assert np.abs(((dev - p0) * nrm).sum(1)).max() < 1e-4 * max(1.0, np.abs(v).max())
-        assert np.array_equal(_bits(E.points_from_mesh(mesh, dx_min=dx, backend='device', context=ctx)), _bits(host))
+        dev, face = check_samples(ctx, v, f, dx)
+        assert dev.shape[0] > 100
         if name in ('fit_quality', 'evaluation_case'):
             tag = 'points_dx' + ('%g' % dx).replace('.', '_')
             assert np.array_equal(_sorted(dev), load_golden(name)[tag])

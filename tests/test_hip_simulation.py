@@ -155,6 +155,26 @@ def test_clusters(ctx):
         assert c.size == sz and (np.diff(c) > 0).all() and np.array_equal(c, R.select_copies(100, sz, 4, S.STREAM_COPY_KEY))
 
 
+SCAN_TILE, SCAN_CHUNK = 2048, 1024          # csrc/nw_bq.hip: elements a workgroup scans, tile sums k_bq_scan_bsums takes before it carries
+
+
+@pytest.mark.parametrize('n,tiles,last_tile', [(1024, 5, 2048), (209715, 1024, 2046), (209716, 1025, 8)])
+def test_clusters_at_the_edges_of_the_scan(ctx, n, tiles, last_tile):
+    """nwg_smlmify scans COPIES * n flags, twice: exactly five tiles; one chunk of tile sums with its last tile partial; the first
+    tile beyond the chunk, whose offset is the carry."""
+    nc = S.COPIES * n
+    assert -(-nc // SCAN_TILE) == tiles and nc - (tiles - 1) * SCAN_TILE == last_tile and (tiles > SCAN_CHUNK) == (n == 209716)
+    rng = np.random.default_rng(8)
+    xyz, sigma = rng.uniform(-500, 500, (n, 3)), rng.uniform(2, 20, (n, 3))
+    want_out, want_sig, want_copy = R.smlmify(xyz, sigma, 33, (S.STREAM_COPY_DISPLACE, S.STREAM_COPY_KEY, S.STREAM_COPY_PHOTONS), **SIGMA_KW)
+    # (want_copy is R.select_copies(n, n, ...))
+    assert want_copy.max() >= (tiles - 1) * SCAN_TILE          # (a copy of the last tile is kept: its slot needs every tile sum before it)
+    out, sig, copy = ctx.smlmify(xyz, sigma, seed=33, **SIGMA_KW)
+    assert out.shape == (n, 3) and sig.shape == (n, 3) and copy.shape == (n,)
+    assert np.array_equal(copy, want_copy)
+    assert np.abs(out - want_out).max() < 1e-9 and np.allclose(sig, want_sig, rtol=1e-12, atol=0)
+
+
 def test_background(ctx):
     kw = dict(density=1, p=0.05, psf_width=(280.0, 280.0, 840.0), mean_photon_count=600, bg_photon_count=20, seed=2, context=ctx)
     shape = ('Torus', dict(radius=100.0, r=30.0, centroid=[600.0, 500.0, 900.0]))
