@@ -1,7 +1,7 @@
 // Density isosurface of the localization cloud on the device (MI355X, gfx950): include/nw_isosurface.h.
 //
 // The start surface of a fit, made from the cloud itself: count per voxel, integer binomial smoothing, a threshold from the median of the
-// occupied voxels, and manifold surface nets of `field > thr`.  The definitions are the header's; the NumPy restatement the kernels are
+// occupied voxels, and sheet-aware surface nets of `field > thr`.  The definitions are the header's; the NumPy restatement the kernels are
 // tested against is tests/isosurface_ref.py.  The scan, the device buffer and the context's scaffolding are the block-boundary units'
 // shared ones (nw_bq.h).
 //

@@ -1,6 +1,6 @@
 """
 The start surface of a fit from the localization cloud itself: ctypes binding of include/nw_isosurface.h (count per voxel, integer
-binomial smoothing, threshold from the median of the occupied voxels, manifold surface nets -- all kernels in libnanowrap_hip.so) and
+binomial smoothing, threshold from the median of the occupied voxels, sheet-aware surface nets -- all kernels in libnanowrap_hip.so) and
 what stands in for the first two modules of upstream's recipe (ch_shrinkwrap/test_evaluation_recipe.yaml:25-38):
 
     pointcloud.Octree -> surface_fitting.DualMarchingCubes(threshold_density, remesh) -> surface_fitting.ShrinkwrapMembrane
@@ -153,8 +153,9 @@ def density_isosurface(points, voxel_size=None, passes=2, threshold_density=None
 
     voxel_size None: pick_voxel_size(points, sigma).  threshold_density (nm^-3, upstream's DualMarchingCubes.threshold_density) None:
     threshold_fraction x the median density of the occupied voxels.  pad: voxels of margin on every side, default passes + 3 (the
-    smoothed field reaches `passes` voxels beyond the outermost localization).  The surface is closed and manifold; it has an inner sheet
-    (inverted, of negative volume) wherever the cloud is a shell: start_surface drops those."""
+    smoothed field reaches `passes` voxels beyond the outermost localization).  The surface is closed and oriented, and manifold on a
+    smoothed density (include/nw_isosurface.h says when not); it has an inner sheet (inverted, of negative volume) wherever the cloud is
+    a shell: start_surface drops those."""
     pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
     passes = int(passes)
     if not 0 <= passes <= MAX_PASSES:

@@ -11,7 +11,11 @@
  *                       independent of the order of the localizations and bit-reproducible.  A density in nm^-3 is field / (4^(3 passes) h^3).
  *   nwi_threshold_auto  thr = floor(fraction * M) (both as doubles), M = the lower median (rank (m - 1) / 2 of the m sorted values) of
  *                       the field over the voxels whose raw count is not zero.
- *   nwi_extract         manifold surface nets of `field > thr` (inside) on the lattice of voxel centres (node (i,j,k) at lo + (i + 1/2) h):
+ *   nwi_extract         sheet-aware surface nets of `field > thr` (inside) on the lattice of voxel centres (node (i,j,k) at lo + (i + 1/2) h),
+ *                       closed and consistently oriented (every mesh edge used an even number of times, as often one way as the other);
+ *                       manifold, every edge used twice, unless two cells that share an ambiguous face (its inside nodes on a diagonal)
+ *                       each join all four crossings of that face in one sheet: the edge between their two vertices is then used four
+ *                       times.  A field smoothed over more than a voxel has no such pair:
  *     - cell (i,j,k), 0 <= i < dims[0] - 1 ..., has the nodes (i + dx, j + dy, k + dz) as corners; its pattern has bit dz*4 + dy*2 + dx set
  *       for an inside corner; cube edge e = axis*4 + a + 2*b runs along `axis` at the offsets a, b along the two other axes u, v
  *       ((u, v, axis) cyclic);

@@ -28,7 +28,8 @@ def edge_ends(e):
     return axis, a, b, u, v, k0, k0 | (1 << axis)
 
 
-def voxels(points, lo, h, dims):
+def voxel_coords(points, lo, h):
+    """floor((x - lo) * (1 / h)) per axis, in float32 and unchecked: what `voxels` and the counting kernel compare with the dimensions"""
     p = np.asarray(points, np.float32).reshape(-1, 3)
     if not np.isfinite(p).all():
         raise ValueError('a localization is not finite')
@@ -36,6 +37,11 @@ def voxels(points, lo, h, dims):
     inv_h = np.float32(1.0) / np.float32(h)
     v = np.floor((p - lo[None, :]) * inv_h)
     assert v.dtype == np.float32
+    return v
+
+
+def voxels(points, lo, h, dims):
+    v = voxel_coords(points, lo, h)
     d = np.asarray(dims, np.int64)
     if (v < 0).any() or (v >= d[None, :].astype(np.float32)).any():
         raise ValueError('a localization lies outside the grid')
@@ -77,9 +83,8 @@ def threshold_auto(field, counts, fraction):
     return int(np.floor(float(fraction) * float(med))), med, int(vals.size)
 
 
-def surface_nets(field, thr, lo, h):
-    """(vertices (V,3) float32, faces (F,3) int32, keys (V,) int64) of field > thr; field is [z, y, x]."""
-    f4 = np.float32
+def cell_patterns(field, thr):
+    """The 8-bit corner pattern of every cell of field > thr, [z, y, x] over the cells"""
     field = np.asarray(field, np.uint64)
     nz, ny, nx = field.shape
     ins = field > np.uint64(thr)
@@ -90,7 +95,16 @@ def surface_nets(field, thr, lo, h):
     for q in range(8):
         dx, dy, dz = q & 1, (q >> 1) & 1, q >> 2
         cfg |= ins[dz:dz + cz, dy:dy + cy, dx:dx + cx].astype(np.int64) << q
-    cfgl = cfg.ravel()
+    return cfg
+
+
+def surface_nets(field, thr, lo, h):
+    """(vertices (V,3) float32, faces (F,3) int32, keys (V,) int64) of field > thr; field is [z, y, x]."""
+    f4 = np.float32
+    field = np.asarray(field, np.uint64)
+    nz, ny, nx = field.shape
+    cx, cy, cz = nx - 1, ny - 1, nz - 1
+    cfgl = cell_patterns(field, thr).ravel()
     active = np.flatnonzero((cfgl != 0) & (cfgl != 255))
     if active.size == 0:
         raise ValueError('no lattice edge crosses the threshold')
@@ -178,6 +192,267 @@ def components(vertices, faces):
     v = np.asarray(vertices, np.float64)
     vol = np.einsum('ij,ij->i', v[f[:, 0]], np.cross(v[f[:, 1]], v[f[:, 2]])) / 6.0
     return [(np.flatnonzero(lab == c), surgery.euler_characteristic(f[lab == c]), float(vol[lab == c].sum())) for c in range(n)]
+
+
+def directed_edges_balanced(faces):
+    """Every directed edge occurs as often as its reverse (with edge_use == 2: a consistently oriented closed surface)"""
+    f = np.asarray(faces, np.int64)
+    e = np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]])
+    m = int(f.max()) + 1
+    fk, fc = np.unique(e[:, 0] * m + e[:, 1], return_counts=True)
+    rk, rc = np.unique(e[:, 1] * m + e[:, 0], return_counts=True)
+    return bool(np.array_equal(fk, rk) and np.array_equal(fc, rc))
+
+
+# ---- device against reference: what the GPU modules share -----------------------------------------------------------------------------
+def position_bound(v):
+    """8 float32 ulp of the largest coordinate (tests/test_isosurface.py derives it)"""
+    return 8 * float(np.spacing(np.float32(np.abs(v).max())))
+
+
+def compare_mesh(name, dev_v, dev_f, dev_k, ref_v, ref_f, ref_k):
+    assert dev_k.shape == ref_k.shape and np.array_equal(dev_k, ref_k)
+    assert dev_f.shape == ref_f.shape and np.array_equal(dev_f, ref_f)
+    err = float(np.abs(dev_v.astype('f8') - ref_v.astype('f8')).max())
+    print(name, 'vertices/faces', dev_v.shape[0], dev_f.shape[0], 'max position difference %.3g nm, bound %.3g nm' % (err, position_bound(ref_v)))
+    assert err <= position_bound(ref_v)
+
+
+def device_chain(pts, h, passes, fraction=0.3, ctx=None, grid=None, thr=None):
+    """density -> threshold_auto -> extract on the device.  grid: (lo, dims) instead of the package's grid rule; thr: extract at this
+    value instead of threshold_auto's."""
+    from ch_shrinkwrap_amd import isosurface as I
+    lo, dims = I.grid_for(pts, h, passes + 3) if grid is None else grid
+    own = ctx is None
+    ctx = I.IsosurfaceContext() if own else ctx
+    try:
+        field, counts = ctx.density(pts, lo, h, dims, passes, return_field=True, return_counts=True)
+        t = ctx.threshold_auto(fraction)
+        v, f, k = ctx.extract(t['thr'] if thr is None else thr, return_keys=True)
+    finally:
+        if own:
+            ctx.close()
+    return dict(lo=lo, dims=dims, field=field, counts=counts, t=t, v=v, f=f, k=k)
+
+
+# ---- small inputs of the edge cases (tests/test_hip_isosurface_edges.py; their premises are checked in tests/test_isosurface.py) ---------
+def noise_counts(seed, dims):
+    """uint32 counts [z, y, x], uniform in 0..3 on the interior and zero on the outermost layer; dims is (x, y, z)"""
+    nx, ny, nz = (int(d) for d in dims)
+    c = np.zeros((nz, ny, nx), np.uint32)
+    c[1:-1, 1:-1, 1:-1] = np.random.default_rng(seed).integers(0, 4, size=(nz - 2, ny - 2, nx - 2))
+    return c
+
+
+def points_from_counts(counts, lo, h, seed=0):
+    """counts[z, y, x] points at the centre of each voxel (float64, rounded to float32 once), shuffled"""
+    c = np.asarray(counts)
+    z, y, x = np.nonzero(c)
+    rep = c[z, y, x].astype(np.int64)
+    idx = np.repeat(np.stack([x, y, z], 1), rep, axis=0).astype(np.float64)
+    pts = (np.asarray(lo, np.float64).reshape(1, 3) + (idx + 0.5) * float(h)).astype(np.float32)
+    np.random.default_rng(seed).shuffle(pts, axis=0)
+    return pts
+
+
+def place(dims, entries):
+    """uint32 counts [z, y, x] with entries {(x, y, z): count}"""
+    nx, ny, nz = (int(d) for d in dims)
+    c = np.zeros((nz, ny, nx), np.uint32)
+    for (x, y, z), n in entries.items():
+        c[z, y, x] = n
+    return c
+
+
+HASH_SLOTS, HASH_PROBES = 2048, 4                                    # the LDS table of k_iso_count
+
+
+def home_slot(v):
+    """First slot a voxel's linear index is tried at: Knuth's multiplicative hash, the top 11 bits of the 32-bit product"""
+    return ((np.asarray(v, np.uint64) * np.uint64(2654435761)) % np.uint64(1 << 32)) >> np.uint64(21)
+
+
+def interior_voxels_with_home(dims, slots, per_slot):
+    """The first `per_slot` interior voxels (ascending linear index) of each home slot in `slots`"""
+    nx, ny, nz = (int(d) for d in dims)
+    z, y, x = np.meshgrid(np.arange(1, nz - 1), np.arange(1, ny - 1), np.arange(1, nx - 1), indexing='ij')
+    lin = ((z * ny + y) * nx + x).ravel()
+    hs = home_slot(lin)
+    return np.concatenate([lin[hs == s][:per_slot] for s in slots])
+
+
+def table_must_overflow(vox):
+    """The pigeonhole premise: the distinct voxels of one workgroup can reach fewer table slots (their home slot and the three after it,
+    modulo the table) than there are voxels, so whatever the order of arrival at least one of them goes to the direct global atomic."""
+    vox = np.unique(np.asarray(vox, np.int64))
+    reach = np.unique((home_slot(vox).astype(np.int64)[:, None] + np.arange(HASH_PROBES)[None, :]) % HASH_SLOTS)
+    return vox.size > reach.size
+
+
+def interleaved_voxel_points(vox, per_voxel, lo, h, dims):
+    """per_voxel points at the centre of each voxel of `vox` (linear indices), voxel by voxel in turn: v0 v1 .. v0 v1 .."""
+    nx, ny = int(dims[0]), int(dims[1])
+    vox = np.tile(np.asarray(vox, np.int64), per_voxel)
+    idx = np.stack([vox % nx, (vox // nx) % ny, vox // (nx * ny)], 1).astype(np.float64)
+    return (np.asarray(lo, np.float64).reshape(1, 3) + (idx + 0.5) * float(h)).astype(np.float32)
+
+
+def face_points(lo, h, n_axis):
+    """Points on voxel faces and one float32 ulp to either side: along each axis in turn the coordinate lo + k h (float64, rounded to
+    float32) for k = 0 .. n_axis - 1, the two other coordinates at voxel centres.  (3 * 3 * n_axis, 3) float32, unfiltered."""
+    lo64 = np.asarray(lo, np.float64).reshape(3)
+    k = np.arange(n_axis)
+    out = []
+    for d in range(3):
+        on = (lo64[d] + k * float(h)).astype(np.float32)
+        for x in (np.nextafter(on, np.float32(-np.inf)), on, np.nextafter(on, np.float32(np.inf))):
+            p = np.empty((n_axis, 3), np.float64)
+            for o in range(3):
+                p[:, o] = lo64[o] + (((7 * k + 3 * o) % n_axis) + 0.5) * float(h)
+            p = p.astype(np.float32)
+            p[:, d] = x
+            out.append(p)
+    return np.concatenate(out)
+
+
+def boundary_point(lo, h, dims, axis, coord):
+    """((1,3) float32 point, its float32 voxel coordinate along `axis`): the centre of voxel `coord` along `axis` (which may be -1 or
+    dims[axis], just outside), the centre of the middle voxel along the two others"""
+    idx = np.asarray(dims, np.float64) // 2 + 0.5
+    idx[axis] = coord + 0.5
+    p = (np.asarray(lo, np.float64) + idx * float(h)).astype(np.float32).reshape(1, 3)
+    return p, int(voxel_coords(p, lo, h)[0, axis])
+
+
+def inside_grid(points, lo, h, dims):
+    """Which points the definition accepts (voxel_coords within the dimensions on every axis)"""
+    v = voxel_coords(points, lo, h)
+    return ((v >= 0) & (v < np.asarray(dims, np.float32)[None, :])).all(1)
+
+
+NOISE_DIMS = (9, 14, 37)                                             # three different axes; 8 * 13 * 36 = 3744 cells pass the scan's 2048 tile
+
+
+@functools.lru_cache(maxsize=None)
+def noise_case(seed, shifted=False):
+    """(points, lo, h, dims, counts) of a noise block at h = 1.  shifted: the same points on a grid that starts one voxel earlier along
+    x, so every voxel's x index, and with it the parity of every quad's lower node, goes up by one."""
+    c = noise_counts(seed, NOISE_DIMS)
+    pts = points_from_counts(c, np.zeros(3), 1.0, seed)
+    if not shifted:
+        return pts, np.zeros(3, np.float32), 1.0, np.array(NOISE_DIMS, np.int32), c
+    c1 = np.concatenate([np.zeros_like(c[:, :, :1]), c], 2)
+    return pts, np.array([-1.0, 0.0, 0.0], np.float32), 1.0, np.array(NOISE_DIMS, np.int32) + np.array([1, 0, 0], np.int32), c1
+
+
+def sheet_census(field, thr):
+    """(set of the patterns present, cells with 0..4 sheets) of field > thr"""
+    cfg = cell_patterns(field, thr).ravel()
+    return set(int(p) for p in np.unique(cfg)), np.bincount(N_SHEETS[cfg], minlength=5)
+
+
+BORDER_GRIDS = {                                                     # counts in corner, edge, face and centre voxels of minimal and thin grids
+    '3x3x3': ((3, 3, 3), {(0, 0, 0): 7, (2, 2, 2): 1, (1, 1, 1): 3}),
+    '3x3x3_edge_face': ((3, 3, 3), {(0, 0, 0): 7, (2, 2, 2): 1, (1, 1, 1): 3, (1, 0, 2): 2, (0, 1, 1): 5}),
+    '3x5x70': ((3, 5, 70), {(0, 0, 0): 7, (2, 4, 69): 1, (1, 2, 35): 3, (0, 2, 69): 2, (1, 0, 0): 4, (2, 2, 1): 6, (1, 4, 34): 5, (1, 2, 68): 9}),
+    '70x3x5': ((70, 3, 5), {(0, 0, 0): 7, (69, 2, 4): 1, (35, 1, 2): 3, (69, 0, 2): 2, (0, 1, 0): 4, (1, 2, 2): 6, (34, 1, 4): 5, (68, 1, 2): 9}),
+}
+
+
+def border_case(name):
+    """(points, lo, h, dims, counts): every value sits on or next to the grid's border"""
+    dims, entries = BORDER_GRIDS[name]
+    c = place(dims, entries)
+    lo = np.array([-20.0, 40.0, 0.0], np.float32)
+    return points_from_counts(c, lo, 10.0, 1), lo, 10.0, np.array(dims, np.int32), c
+
+
+def _interior(dims, values, seed):
+    """counts with `values` in interior voxels picked at random"""
+    nx, ny, nz = dims
+    inner = (nx - 2) * (ny - 2) * (nz - 2)
+    sel = np.random.default_rng(seed).permutation(inner)[:len(values)]
+    c = np.zeros((nz, ny, nx), np.uint32)
+    z, r = np.divmod(sel, (ny - 2) * (nx - 2))
+    y, x = np.divmod(r, nx - 2)
+    c[z + 1, y + 1, x + 1] = np.asarray(values, np.uint32)
+    return c
+
+
+SELECT_DIMS = (12, 12, 12)
+SELECT_VALUES = {                                                    # field values of the occupied voxels at passes = 0
+    'one': [5],
+    'two': [3, 9],
+    'all_equal': [6] * 7,
+    'odd': [1, 2, 4, 8, 16],
+    'even': [1, 2, 4, 8, 16, 32],                                    # lower median 4, upper 8
+    'even_tie': [2, 4, 4, 4, 4, 9],                                  # ties across the median
+    'byte_ff': [254, 255, 255, 256, 257],                            # the median's low byte is 0xFF: the last bin of the second pass
+    'ff_100': [255, 256],                                            # lower median 255, next to a carry into the second byte
+    'three_bytes': [65535, 65536, 65536, 70000, 3],                  # n >= 65 536: the select starts at shift 16; median 65 536 = 01 00 00
+    'three_bytes_ffff': [65535, 65535, 65536, 70000, 3, 2],          # median 65 535 = 00 FF FF: the last bin twice
+    'many': [255] * 300 + [256] * 299,                               # median 255 by one voxel
+}
+
+
+def select_case(name):
+    """(points, lo, h, dims, counts)"""
+    c = _interior(SELECT_DIMS, SELECT_VALUES[name], 11)
+    lo = np.zeros(3, np.float32)
+    return points_from_counts(c, lo, 1.0, 2), lo, 1.0, np.array(SELECT_DIMS, np.int32), c
+
+
+def excluded_case():
+    """passes = 2: a voxel of count 1 beside one of count 1000, and one of count 1 far away.  The empty neighbours of the 1000 have a
+    larger field than the far voxel and must stay out of the median."""
+    dims = (16, 12, 12)
+    c = place(dims, {(5, 6, 6): 1000, (6, 6, 6): 1, (11, 5, 5): 1})
+    lo = np.zeros(3, np.float32)
+    return points_from_counts(c, lo, 1.0, 3), lo, 1.0, np.array(dims, np.int32), c
+
+
+def big_field_case():
+    """passes = 5: blobs of 6000 and 5000 points in voxels 4 apart, padded by 8.  The centre weight of five rounds is C(10, 5)^3 = 252^3,
+    so the peaks are near 9.6e10 and 8e10, above 2^32."""
+    dims = (21, 17, 17)
+    c = place(dims, {(8, 8, 8): 6000, (12, 8, 8): 5000})
+    lo = np.array([5e3, -3e3, 1e3], np.float32)
+    return points_from_counts(c, lo, 10.0, 4), lo, 10.0, np.array(dims, np.int32), c
+
+
+CARRY_DIMS = (130, 130, 130)                                         # 129^3 = 2 146 689 cells: past 2^21, the first carry of the scan's tile sums
+
+
+@functools.lru_cache(maxsize=None)
+def carry_case():
+    """(points, lo, h, dims, counts): a 6^3 noise block near the origin and one in the far corner, whose cells have linear indices above 2^21"""
+    nx, ny, nz = CARRY_DIMS
+    c = np.zeros((nz, ny, nx), np.uint32)
+    c[2:8, 3:9, 4:10] = noise_counts(21, (8, 8, 8))[1:-1, 1:-1, 1:-1]
+    c[122:128, 121:127, 120:126] = noise_counts(22, (8, 8, 8))[1:-1, 1:-1, 1:-1]
+    lo = np.zeros(3, np.float32)
+    return points_from_counts(c, lo, 1.0, 5), lo, 1.0, np.array(CARRY_DIMS, np.int32), c
+
+
+HASH_DIMS = (64, 64, 64)
+
+
+def hash_case(slots, per_slot, per_voxel=100):
+    """(points, lo, h, dims, voxels): per_voxel points in each of per_slot interior voxels of every home slot in `slots`, interleaved, so
+    that every voxel appears among the first 1024 points (one workgroup of the counting kernel)"""
+    vox = interior_voxels_with_home(HASH_DIMS, slots, per_slot)
+    lo = np.zeros(3, np.float32)
+    return interleaved_voxel_points(vox, per_voxel, lo, 1.0, HASH_DIMS), lo, 1.0, np.array(HASH_DIMS, np.int32), vox
+
+
+def spread_points(n, seed=7):
+    """n points over a few hundred voxels of a 20 x 18 x 16 grid, h = 7.3, off the origin: (points, lo, h, dims)"""
+    dims = np.array([20, 18, 16], np.int32)
+    lo, h = np.array([5e3, -3e3, 1e3], np.float32), 7.3
+    rng = np.random.default_rng(seed)
+    cells = rng.integers(1, dims - 1, size=(300, 3))
+    idx = cells[rng.integers(0, 300, size=n)] + rng.uniform(0.05, 0.95, size=(n, 3))
+    return (lo.astype(np.float64)[None, :] + idx * h).astype(np.float32), lo, h, dims
 
 
 # ---- the scenes of the tests (generated once per session) ---------------------------------------------------------------------------------

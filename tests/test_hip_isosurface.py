@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import isosurface_ref as R
-from isosurface_ref import scene, reference
+from isosurface_ref import scene, reference, device_chain, position_bound, compare_mesh as _compare_mesh
 from ch_shrinkwrap_amd import isosurface as I
 from ch_shrinkwrap_amd import synth
 
@@ -25,25 +25,6 @@ def cloud(name):
         return pts.astype('f4'), 10.0, 4
     pts, _, h = scene(name)
     return pts, h, 2
-
-
-def device_chain(pts, h, passes, fraction=0.3, ctx=None):
-    lo, dims = I.grid_for(pts, h, passes + 3)
-    own = ctx is None
-    ctx = I.IsosurfaceContext() if own else ctx
-    try:
-        field, counts = ctx.density(pts, lo, h, dims, passes, return_field=True, return_counts=True)
-        t = ctx.threshold_auto(fraction)
-        v, f, k = ctx.extract(t['thr'], return_keys=True)
-    finally:
-        if own:
-            ctx.close()
-    return dict(lo=lo, dims=dims, field=field, counts=counts, t=t, v=v, f=f, k=k)
-
-
-def position_bound(v):
-    """8 float32 ulp of the largest coordinate (tests/test_isosurface.py derives it)"""
-    return 8 * float(np.spacing(np.float32(np.abs(v).max())))
 
 
 @pytest.mark.parametrize('name', ['c1', 'c4', 'c1_translated', 'one_voxel'])
@@ -67,14 +48,6 @@ def test_field_and_threshold_are_bit_identical(name):
     print(name, 'dims', dims, 'median', med, 'thr', thr, 'occupied', occ)
     assert (t['median'], t['thr'], t['n_occupied']) == (med, thr, occ)
     assert np.isclose(t['threshold_density'], thr / I.field_scale(h, passes), rtol=1e-12)
-
-
-def _compare_mesh(name, dev_v, dev_f, dev_k, ref_v, ref_f, ref_k):
-    assert dev_k.shape == ref_k.shape and np.array_equal(dev_k, ref_k)
-    assert dev_f.shape == ref_f.shape and np.array_equal(dev_f, ref_f)
-    err = float(np.abs(dev_v.astype('f8') - ref_v.astype('f8')).max())
-    print(name, 'vertices/faces', dev_v.shape[0], dev_f.shape[0], 'max position difference %.3g nm, bound %.3g nm' % (err, position_bound(ref_v)))
-    assert err <= position_bound(ref_v)
 
 
 @pytest.mark.parametrize('name', ['c1', 'c4', 'c1_translated'])

@@ -231,7 +231,167 @@ def test_two_sheets_through_one_cell_do_not_share_a_vertex():
     assert v.shape[0] == 2 * 8 and f.shape[0] == 2 * 12
 
 
+# ---- the premises of the edge cases (tests/test_hip_isosurface_edges.py), on the reference alone ----------------------------------------
+NOISE_SEEDS = (0, 1, 2)
+
+
+@pytest.mark.parametrize('seed', NOISE_SEEDS)
+def test_noise_fields_reach_every_pattern_and_every_sheet_count(seed):
+    """Counts uniform in 0..3 at thr = 1: all 256 patterns, cells with two, three and four sheets, a quarter of the nodes equal to thr.
+    The nets of such a field are closed and oriented but not manifold: an edge is used twice or four times (README, start surface)."""
+    pts, lo, h, dims, counts = R.noise_case(seed)
+    assert np.array_equal(R.count(pts, lo, h, dims), counts) and counts[1:-1, 1:-1, 1:-1].max() == 3
+    assert len(set(int(d) for d in dims)) == 3 and int(np.prod(dims - 1)) > 2048
+    field = R.smooth(counts, 0)
+    patterns, sheets = R.sheet_census(field, 1)
+    print('seed', seed, 'points', pts.shape[0], 'cells with 0..4 sheets', sheets.tolist(), 'nodes equal to thr', int((field == 1).sum()))
+    assert patterns == set(range(256)) and (sheets[2:] >= 1).all()
+    assert 0.2 < (field[1:-1, 1:-1, 1:-1] == 1).mean() < 0.3
+    v, f, keys = R.surface_nets(field, 1, lo, h)
+    use = R.edge_use(f)
+    assert (use % 2 == 0).all() and set(use.tolist()) == {2, 4}
+    assert R.directed_edges_balanced(f)
+    assert not R.directed_edges_balanced(f[:-1])                               # (the measure does tell)
+    # one voxel earlier along x: the same surface, the other diagonal of every quad
+    pts1, lo1, _, dims1, counts1 = R.noise_case(seed, shifted=True)
+    assert np.array_equal(R.count(pts1, lo1, h, dims1), counts1)
+    v1, f1, _ = R.surface_nets(R.smooth(counts1, 0), 1, lo1, h)
+    assert f1.shape == f.shape and float(np.abs(v1.astype('f8') - v.astype('f8')).max()) <= R.position_bound(v)     # (lo - 1 + (i + 1) rounds apart from lo + i)
+    assert np.array_equal(f1[0::2, 0], f[0::2, 0]) and (f1[0::2, 2] != f[0::2, 2]).all()
+
+
+@pytest.mark.parametrize('seed', NOISE_SEEDS)
+def test_reference_agrees_with_isosurface_mesh_on_every_pattern(seed):
+    """The noise fields through the package's other mesher, as test_reference_agrees_with_isosurface_mesh_on_the_same_field does for the
+    smooth scenes (same bound, same derivation).  Both use an edge four times where two cells share an ambiguous face."""
+    pts, lo, h, dims, counts = R.noise_case(seed)
+    field = R.smooth(counts, 0)
+    v, f, keys = R.surface_nets(field, 1, lo, h)
+    sdf, origin = _lattice_sdf(field, lo, h)
+    mv, mf = synth.isosurface_mesh(sdf, origin, origin + (dims - 1.5) * h, h, level=-1.0, slack=1e30, project=0)
+    assert mv.shape == v.shape and mf.shape == f.shape
+    tol = R.position_bound(v)
+    err = float(np.abs(mv.astype('f8') - v.astype('f8')).max())
+    print('seed', seed, 'vertices/faces', v.shape[0], f.shape[0], 'max position difference %.3g, bound %.3g' % (err, tol))
+    assert err <= tol
+    from ch_shrinkwrap_amd.surgery import euler_characteristic
+    assert euler_characteristic(mf) == euler_characteristic(f)
+    assert np.array_equal(np.sort(R.edge_use(mf)), np.sort(R.edge_use(f)))
+
+
+@pytest.mark.parametrize('name', sorted(R.BORDER_GRIDS))
+def test_border_grids_lose_mass_at_the_border(name):
+    pts, lo, h, dims, counts = R.border_case(name)
+    assert np.array_equal(R.count(pts, lo, h, dims), counts)
+    n = pts.shape[0]
+    assert counts[0, 0, 0] > 0 and counts[-1, -1, -1] > 0                       # two corners of the grid
+    for passes in (0, 1, 5):
+        field = R.smooth(counts, passes)
+        mass = n * 4 ** (3 * passes)
+        assert int(field.sum()) == mass if passes == 0 else int(field.sum()) < mass
+        if name == '3x3x3' and passes == 5:
+            assert (int(field.sum()), mass) == (1023641088, 11811160064)
+        with pytest.raises(ValueError, match='outermost'):
+            R.surface_nets(field, 0, lo, h)
+
+
+def test_hash_cases_must_overflow_the_table_and_wrap_it():
+    lin = np.arange(64 ** 3)
+    assert int(R.home_slot(1)) == 2654435761 >> 21 and int(R.home_slot(123457)) == ((123457 * 2654435761) % 2 ** 32) >> 21
+    per_slot = np.bincount(R.home_slot(lin).astype(np.int64), minlength=2048)
+    assert per_slot.min() == 126 and per_slot.max() == 131
+    for slots, per in (((1000,), 8), ((2047,), 8), ((2045, 2046, 2047), 3)):
+        pts, lo, h, dims, vox = R.hash_case(slots, per)
+        assert np.unique(vox).size == vox.size == per * len(slots)
+        assert sorted(set(R.home_slot(vox).tolist())) == list(slots)
+        xyz = np.stack([vox % 64, (vox // 64) % 64, vox // 4096], 1)
+        assert xyz.min() >= 1 and xyz.max() <= 62                               # interior
+        assert R.table_must_overflow(vox)
+        first = R.voxels(pts[:1024], lo, h, dims)
+        assert np.unique((first[:, 2] * 64 + first[:, 1]) * 64 + first[:, 0]).size == vox.size      # all of them in the first workgroup
+        assert np.array_equal(np.flatnonzero(R.count(pts, lo, h, dims).ravel()), np.sort(vox))
+    assert (R.home_slot(R.interior_voxels_with_home(R.HASH_DIMS, (2047,), 1000)) == 2047).sum() == 112
+    assert not R.table_must_overflow(R.interior_voxels_with_home(R.HASH_DIMS, (1000,), 4))
+    # two voxels of home slot 2047 cannot both stay there: one probes slot 0
+    assert (R.home_slot(R.hash_case((2045, 2046, 2047), 3)[4]) == 2047).sum() >= 2
+
+
+FACE_H = (0.1, 7.3, 12.0)
+FACE_LO = ((0.0, 0.0, 0.0), (5e3, -3e3, 1e3))
+
+
+@pytest.mark.parametrize('h', FACE_H)
+@pytest.mark.parametrize('lo', FACE_LO)
+def test_points_on_voxel_faces_mostly_stay_inside(h, lo):
+    """The reference alone says which of the face points fall outside the 40^3 grid; fewer than 5 % do."""
+    dims = np.array([40, 40, 40], np.int32)
+    pts = R.face_points(lo, h, 40)
+    keep = R.inside_grid(pts, lo, h, dims)
+    v = R.voxel_coords(pts, lo, h)
+    print('h', h, 'lo', lo, 'dropped', int((~keep).sum()), 'of', pts.shape[0], 'voxel coordinates', v.min(), '...', v.max())
+    assert pts.shape == (360, 3) and (~keep).mean() < 0.05
+    R.count(pts[keep], lo, h, dims)
+    # one ulp below a face is the voxel before it, except where rounding says otherwise (at lo = 0 and h = 7.3 the point one ulp below
+    # zero scales to -0 and stays in voxel 0); 1 / h is inexact in float32 for every h here
+    k = np.arange(40)
+    below, on = v[:40, 0], v[40:80, 0]
+    assert (below <= on).all() and (below < on).any() and np.abs(on - k).max() <= 1
+    assert float(np.float32(1.0) / np.float32(h)) != 1.0 / float(np.float32(h))
+    for edge, ok in ((dims - 1, True), (dims, False), (np.array([-1, -1, -1]), False)):
+        for d in range(3):
+            p, coord = R.boundary_point(lo, h, dims, d, int(edge[d]))
+            assert coord == edge[d] and bool(R.inside_grid(p, lo, h, dims)[0]) == ok
+
+
+def test_select_cases_have_the_medians_they_are_named_for():
+    want = {'one': 5, 'two': 3, 'all_equal': 6, 'odd': 4, 'even': 4, 'even_tie': 4, 'byte_ff': 255, 'ff_100': 255, 'three_bytes': 65536,
+            'three_bytes_ffff': 65535, 'many': 255}
+    assert sorted(want) == sorted(R.SELECT_VALUES)
+    for name, med in want.items():
+        pts, lo, h, dims, counts = R.select_case(name)
+        assert np.array_equal(R.count(pts, lo, h, dims), counts)
+        assert sorted(counts[counts > 0].tolist()) == sorted(R.SELECT_VALUES[name])
+        assert counts[0].max() == counts[-1].max() == counts[:, 0].max() == counts[:, -1].max() == counts[:, :, 0].max() == counts[:, :, -1].max() == 0
+        thr, m, occ = R.threshold_auto(R.smooth(counts, 0), counts, 1.0)
+        assert (thr, m, occ) == (med, med, len(R.SELECT_VALUES[name])), name
+        if name.startswith('three_bytes'):
+            assert pts.shape[0] >= 65536                                        # the select starts at shift 16
+    sv = sorted(R.SELECT_VALUES['even'])
+    assert sv[(len(sv) - 1) // 2] != sv[len(sv) // 2]
+    pts, lo, h, dims, counts = R.excluded_case()
+    field = R.smooth(counts, 2)
+    assert field[counts == 0].max() > field[counts > 0].min()                   # an empty voxel denser than an occupied one
+    assert R.threshold_auto(field, counts, 1.0)[1:] == (int(np.sort(field[counts > 0])[1]), 3)
+    assert int(np.sort(field[field > 0])[(int((field > 0).sum()) - 1) // 2]) != R.threshold_auto(field, counts, 1.0)[1]
+
+
+def test_big_field_case_is_above_32_bits_and_smooth():
+    pts, lo, h, dims, counts = R.big_field_case()
+    field, c = R.density(pts, lo, h, dims, 5)
+    assert np.array_equal(c, counts) and int(field.max()) > 2 ** 32
+    peaks = sorted(int(x) for x in field[counts > 0])
+    assert peaks[0] > 5000 * 252 ** 3 and peaks[1] > 6000 * 252 ** 3 and peaks[0] < peaks[1]
+    thr = R.threshold_auto(field, counts, 0.3)[0]
+    assert thr > 2 ** 32
+    for t, ncomp in ((thr, None), ((peaks[0] + peaks[1]) // 2, 1)):
+        v, f, k = R.surface_nets(field, t, lo, h)
+        assert (R.edge_use(f) == 2).all() and R.directed_edges_balanced(f)
+        if ncomp:
+            assert len(R.components(v, f)) == ncomp
+
+
+def test_carry_case_has_cells_past_two_to_the_21():
+    import time
+    pts, lo, h, dims, counts = R.carry_case()
+    assert np.array_equal(R.count(pts, lo, h, dims), counts)
+    t0 = time.time()
+    v, f, keys = R.surface_nets(R.smooth(counts, 0), 1, lo, h)
+    print('reference on 130^3: %.2f s, %d vertices' % (time.time() - t0, v.shape[0]))
+    cells = keys // 16
+    assert int(np.prod(dims - 1)) > 2 ** 21 and (cells < 2 ** 21).any() and (cells > 2 ** 21).any()
+
+
 def test_gpu_tests_read_nothing_outside_the_repository():
-    for name in ('test_hip_isosurface.py', 'isosurface_ref.py'):
+    for name in ('test_hip_isosurface.py', 'test_hip_isosurface_edges.py', 'isosurface_ref.py'):
         src = open(os.path.join(ROOT, 'tests', name)).read()
         assert '/root/' + 'reference' not in src and 'oracle/' + '_ref' not in src and '_' + 'ref/' not in src, name
