@@ -426,6 +426,10 @@ int check_program(const nwg_op *ops, int n_ops, std::string *why)
         for (int k = 0; k < n_args[code]; ++k)
             if (!std::isfinite(ops[o].a[k])) { *why = "op " + std::to_string(o) + ": a non-finite argument"; return NWG_ERR_BADARG; }
         if (code == NWG_OP_FRAME) continue;
+        if (code == NWG_OP_CAPSULE) {                          // sdf.capsule divides by |b - a|^2: 0 / 0 at every point of a capsule without length
+            const double bx = ops[o].a[3] - ops[o].a[0], by = ops[o].a[4] - ops[o].a[1], bz = ops[o].a[5] - ops[o].a[2];
+            if (!((bx * bx + by * by) + bz * bz > 0.0)) { *why = "op " + std::to_string(o) + ": a capsule whose ends coincide"; return NWG_ERR_BADARG; }
+        }
         if (code >= NWG_OP_UNION) {
             if (ops[o].a[0] < 0.0) { *why = "op " + std::to_string(o) + ": negative k"; return NWG_ERR_BADARG; }
             if (depth < 2) { *why = "op " + std::to_string(o) + ": a combinator with fewer than two values on the stack"; return NWG_ERR_BADARG; }

@@ -170,6 +170,8 @@ def Torus(radius=2, r=0.05, **kw):
 def Capsule(start, end, radius=1, **kw):
     a, b = _vec(start), _vec(end)
     length = float(np.sqrt(((b - a) ** 2).sum()))
+    if not ((b - a) ** 2).sum() > 0:                         # sdf.capsule (sdf.py:75) divides by it: NaN everywhere upstream, refused here
+        raise ValueError('a capsule whose ends coincide has no axis: start %r, end %r' % (list(a), list(b)))
     return _Primitive(OP_CAPSULE, list(a) + list(b) + [radius], _centroid(kw) + 0.5 * (a + b), length / 2.0 + radius, 0.5 * (a + b),
                       length / 2.0 + float(radius), False)
 

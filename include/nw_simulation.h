@@ -96,7 +96,8 @@ void nwg_destroy(nwg_ctx *ctx);
 const char *nwg_last_error(nwg_ctx *ctx);
 
 /* The shape of every later call (shape.py's classes, compiled by the host: ch_shrinkwrap_amd/simulation.py compile_shape).  Checked here:
- * 1..NWG_MAX_OPS ops, known codes, finite arguments, k >= 0, the stack never deeper than NWG_STACK_DEPTH or empty under a combinator,
+ * 1..NWG_MAX_OPS ops, known codes, finite arguments, k >= 0, a capsule's two ends apart (|b - a|^2 > 0 in float64: sdf.capsule divides by
+ * it, and upstream's result for a == b is NaN at every point), the stack never deeper than NWG_STACK_DEPTH or empty under a combinator,
  * exactly one value left at the end. */
 int nwg_set_program(nwg_ctx *ctx, const nwg_op *ops, int n_ops);
 
