@@ -29,7 +29,8 @@ _BASE = ['-O3', '--offload-arch=gfx950', '-fPIC', '-fvisibility=hidden']
 # the block-boundary query units: no contraction, as the pairing kernel and the half-edge lengths must round every product as the
 # reference's C loop and TriMesh's NumPy do (their results are bit-identical)
 _QUERY = _BASE + ['-ffp-contract=off', '-Wall', '-Wno-unused-function']
-_BQ = [_csrc('nw_bq.h'), _csrc('nw_device.h')]            # (nw_device.h: nw_wave_incl_scan)
+_BQ_H = [_csrc('nw_bq.h'), _csrc('nw_bq_core.h')]         # (nw_bq.h includes its HIP-free part, nw_bq_core.h)
+_BQ = _BQ_H + [_csrc('nw_device.h')]                      # (nw_device.h: nw_wave_incl_scan)
 
 OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_BQ = _csrc('nanowrap.o'), _csrc('nw_holepunch.o'), _csrc('nw_surgery.o'), _csrc('nw_bq.o')
 OBJ_ISOSURFACE = _csrc('nw_isosurface.o')
@@ -37,8 +38,9 @@ OBJ_EVALUATION = _csrc('nw_evaluation.o')
 OBJ_SIMULATION = _csrc('nw_simulation.o')
 # the translation units of libnanowrap_hip.so: (source, object, what else it is rebuilt for, flags).  The objects are linked in this order.
 UNITS = [
-    # the per-iteration kernels and the C-ABI; every header of csrc/ but nw_bq.h is included by it (directly or through nw_kernels.h)
-    (_csrc('nanowrap.hip'), OBJ_MAIN, sorted(set(glob.glob(_csrc('*.h'))) - {_csrc('nw_bq.h')}) + [_include('nanowrap.h')],
+    # the per-iteration kernels and the C-ABI; every header of csrc/ but nw_bq.h and nw_bq_core.h is included by it (directly or through
+    # nw_kernels.h)
+    (_csrc('nanowrap.hip'), OBJ_MAIN, sorted(set(glob.glob(_csrc('*.h'))) - set(_BQ_H)) + [_include('nanowrap.h')],
      [f for f in HIPCC_FLAGS if f != '-shared']),
     # set-up radix sort (hipCUB)
     (_csrc('nw_sort.hip'), _csrc('nw_sort.o'), [], _BASE + ['-Wno-unused-value']),
@@ -46,17 +48,17 @@ UNITS = [
     (_csrc('nw_remesh_dev.hip'), _csrc('nw_remesh_dev.o'), [_include('nanowrap.h')],
      _BASE + ['-ffp-contract=off', '-Wall', '-Wno-unused-value', '-Wno-unused-function']),
     # the hole-punch point queries
-    (_csrc('nw_holepunch.hip'), OBJ_HOLEPUNCH, [_include('nw_holepunch.h'), _csrc('nw_bq.h')], _QUERY),
+    (_csrc('nw_holepunch.hip'), OBJ_HOLEPUNCH, [_include('nw_holepunch.h')] + _BQ_H, _QUERY),
     # the neck / short-edge / inner-surface queries
     (_csrc('nw_surgery.hip'), OBJ_SURGERY, [_include('nw_surgery.h')] + _BQ, _QUERY),
     # the density isosurface of the cloud (the start surface of a fit)
-    (_csrc('nw_isosurface.hip'), OBJ_ISOSURFACE, [_include('nw_isosurface.h'), _csrc('nw_bq.h')], _QUERY),
+    (_csrc('nw_isosurface.hip'), OBJ_ISOSURFACE, [_include('nw_isosurface.h')] + _BQ_H, _QUERY),
     # the fit-quality metric: mesh sampling and nearest neighbours between two clouds (nw_evaluation_core.h: the sampler's arithmetic,
     # which the tests also compile for the CPU)
-    (_csrc('nw_evaluation.hip'), OBJ_EVALUATION, [_include('nw_evaluation.h'), _csrc('nw_bq.h'), _csrc('nw_evaluation_core.h')], _QUERY),
+    (_csrc('nw_evaluation.hip'), OBJ_EVALUATION, [_include('nw_evaluation.h'), _csrc('nw_evaluation_core.h')] + _BQ_H, _QUERY),
     # the SMLM cloud simulator: a shape's signed distance as a postfix program, the surface lattice, the localization model
-    (_csrc('nw_simulation.hip'), OBJ_SIMULATION, [_include('nw_simulation.h'), _csrc('nw_bq.h')], _QUERY),
-    # what the five above share (csrc/nw_bq.h): the exclusive scan
+    (_csrc('nw_simulation.hip'), OBJ_SIMULATION, [_include('nw_simulation.h')] + _BQ_H, _QUERY),
+    # what the five above share (csrc/nw_bq.h): the exclusive scan and the point grid's bounding box and counting sort, float and double
     (_csrc('nw_bq.hip'), OBJ_BQ, _BQ, _QUERY),
 ]
 DEPS = sorted(set(d for src, _, extra, _ in UNITS for d in [src] + extra))
@@ -109,9 +111,6 @@ KERNEL_BUDGETS = {
     'k_hp_empty_faces':               (64, 0),
     'k_hp_pair':                      (64, 8 * 1024),      # two LDS tiles of 256 float4 (centroids, normals)
     'k_hp_prism':                     (176, 0),            # six float64 half-planes and two centres live across the cell walk (3 waves per SIMD)
-    'k_hp_cell_count':                (32, 0),
-    'k_hp_scatter':                   (32, 0),
-    'k_hp_bbox':                      (32, 0),
     'k_hp_cand_geom':                 (32, 0),
     'k_hp_pair_final':                (16, 0),
     # neck removal / short-edge cleanup / inner surfaces (csrc/nw_surgery.o): block-boundary queries, budgeted for zero scratch
@@ -141,9 +140,6 @@ KERNEL_BUDGETS = {
     'k_ev_face_setup':                (64, 0),             # the float32 set-up of a face: 23 values live until they are stored
     'k_ev_node_test':                 (32, 0),
     'k_ev_emit':                      (32, 0),
-    'k_ev_bbox':                      (48, 0),             # six 64-bit keys per thread
-    'k_ev_cell_count':                (48, 0),
-    'k_ev_scatter':                   (16, 0),
     'k_ev_nearest':                   (64, 64),            # float64 query, best pair and the ring walk's bounds: 8 waves per SIMD; LDS = the four waves' sums
     'k_ev_sum_final':                 (16, 64),
     # the SMLM cloud simulator (csrc/nw_simulation.o): set-up kernels in float64, budgeted for zero scratch (the interpreter's value stack
@@ -162,10 +158,16 @@ KERNEL_BUDGETS = {
     'k_sim_copy_equal':               (16, 0),
     'k_sim_copy_keep':                (16, 0),
     'k_sim_copy_emit':                (88, 0),             # three normals and three photon draws per copy, unrolled: 5 waves per SIMD
-    # the exclusive scan they share (csrc/nw_bq.o)
+    # what the five units above share (csrc/nw_bq.o): the exclusive scan, and the point grid of hole punching (f32) and of the metric (f64)
     'k_bq_scan_tiles':                (32, 1024),
     'k_bq_scan_bsums':                (32, 1024),
     'k_bq_scan_final':                (32, 1024),
+    'k_bq_bbox_f32':                  (32, 0),
+    'k_bq_cell_count_f32':            (32, 0),
+    'k_bq_scatter_f32':               (32, 0),
+    'k_bq_bbox_f64':                  (48, 0),             # six 64-bit keys per thread
+    'k_bq_cell_count_f64':            (48, 0),
+    'k_bq_scatter_f64':               (16, 0),
 }
 BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_BQ]
 

@@ -1,16 +1,22 @@
-// What the block-boundary query units (nw_holepunch.hip, nw_surgery.hip) share: the device buffer, the base of their contexts with its
-// create / destroy / last_error bodies, the HIP-call macro, the host check of a mesh, the ordered-int map and the exclusive scan
-// (kernels and host entry in nw_bq.hip).  Each C-ABI keeps its own status codes: what needs one takes it from its user.
+// What the query units (nw_holepunch.hip, nw_surgery.hip, nw_isosurface.hip, nw_evaluation.hip, nw_simulation.hip) share: the device
+// buffer and the staging of host arrays into it, the base of their contexts with its create / destroy / last_error bodies, the HIP-call
+// macro, the host checks of a mesh and of finiteness, the ordered-key maps, the exclusive scan, the point grid (bounding box, sizing,
+// counting sort by cell, the cell index of a coordinate) in float and in double, and the host loop of the 64-bit radix select.  Kernels
+// and host entries are in nw_bq.hip; what needs no HIP is in nw_bq_core.h.  Each C-ABI keeps its own status codes and error texts:
+// everything here that can fail returns a hipError_t or a flag, and its user says what that means.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cmath>
 #include <string>
 #include <algorithm>
+#include <numeric>
+
+#include "nw_bq_core.h"
 
 namespace bq {
 
-// monotone float <-> int map (atomicMin / atomicMax on floats)
+// monotone float <-> int and double <-> 64-bit maps (atomicMin / atomicMax on floating-point values)
 __host__ __device__ __forceinline__ int enc_ord(float f)
 {
     const int i = __builtin_bit_cast(int, f);
@@ -18,6 +24,17 @@ __host__ __device__ __forceinline__ int enc_ord(float f)
 }
 
 __host__ __device__ __forceinline__ float dec_ord(int v) { return __builtin_bit_cast(float, v >= 0 ? v : v ^ 0x7fffffff); }
+
+__host__ __device__ __forceinline__ unsigned long long enc_ord(double d)
+{
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, d);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
+__host__ __device__ __forceinline__ double dec_ord(unsigned long long e)
+{
+    return __builtin_bit_cast(double, (e >> 63) ? (e ^ 0x8000000000000000ull) : ~e);
+}
 
 struct DevBuf {
     void *p = nullptr;
@@ -59,6 +76,9 @@ inline int fail(Ctx *ctx, int code, const std::string &msg)
             return bq::fail(ctx, e_ == hipErrorOutOfMemory ? (ERR_NOMEM) : (ERR_HIP), std::string(#call) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+// (for what returns a hipError_t itself)
+#define BQ_TRY(call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return e_; } while (0)
+
 inline int nblk(int64_t n, int b = 256) { return (int)((n + b - 1) / b); }
 
 template <class C> int create(int device, C **out, int err_badarg, int err_hip)
@@ -88,18 +108,105 @@ template <class C> void destroy(C *ctx)
 
 inline const char *last_error(const Ctx *ctx) { return ctx ? ctx->err.c_str() : "null ctx"; }
 
+// ---- host arrays ------------------------------------------------------------------------------------------------------------------------
+template <class T> bool all_finite(const T *p, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(p[i])) return false;
+    return true;
+}
+
 // host-side check of the mesh arguments (before any HIP call): sizes within the limits of the int kernels, pos finite, faces in range
 inline bool mesh_ok(const float *pos, int64_t nv, const int32_t *faces, int64_t nf)
 {
     if (!pos || !faces || nv < 3 || nf < 1 || nv > (1ll << 30) || nf > (1ll << 29)) return false;
-    for (int64_t i = 0; i < 3 * nv; ++i)
-        if (!std::isfinite(pos[i])) return false;
+    if (!all_finite(pos, 3 * nv)) return false;
     for (int64_t i = 0; i < 3 * nf; ++i)
         if (faces[i] < 0 || faces[i] >= nv) return false;
     return true;
 }
 
-// exclusive scan of in[0..n) on `stream`: out[0..n] with out[n] = the total; tmp holds the tile sums (nw_bq.hip)
+// src[0..n) into buf on `stream` (the copy is asynchronous: src must outlive the stream's next synchronisation)
+template <class T> hipError_t upload(hipStream_t stream, DevBuf &buf, const T *src, int64_t n)
+{
+    BQ_TRY(buf.ensure(sizeof(T) * (size_t)n));
+    return hipMemcpyAsync(buf.p, src, sizeof(T) * (size_t)n, hipMemcpyHostToDevice, stream);
+}
+
+// whether kernels can read p in place (device memory); a host pointer is to be uploaded first
+inline bool on_device(const void *p)
+{
+    hipPointerAttribute_t attr;
+    const bool dev = hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeDevice;
+    (void)hipGetLastError();                                  // (a host pointer leaves an error behind on some runtimes)
+    return dev;
+}
+
+// ---- exclusive scan (nw_bq.hip) ---------------------------------------------------------------------------------------------------------
+// exclusive scan of in[0..n) on `stream`: out[0..n] with out[n] = the total; tmp holds the tile sums
 hipError_t scan_exclusive(hipStream_t stream, const int *in, int n, int *out, DevBuf &tmp);
+
+// the same, and out[n] read back into *total: the stream is synchronised.  What range the total may lie in is its user's to check.
+hipError_t scan_total(hipStream_t stream, const int *in, int n, int *out, DevBuf &tmp, int *total);
+
+// ---- point grid (nw_bq.hip), T = float or double ----------------------------------------------------------------------------------------
+// a cloud's bounding box cut into cubes of side h; cell (x, y, z) has the id (z * dims[1] + y) * dims[0] + x
+template <class T> struct Grid {
+    T lo[3], hi[3];
+    T h;
+    int dims[3];
+    int64_t cells() const { return (int64_t)dims[0] * dims[1] * dims[2]; }
+};
+
+// the ordered key of a coordinate, and a point in cell order: a float cloud keeps its coordinates only ({x, y, z, 0}), a double cloud also
+// the index in the caller's array
+struct PtF64 { double x, y, z; long long i; };
+template <class T> struct GridOf;
+template <> struct GridOf<float> { typedef int key; typedef float4 point; };
+template <> struct GridOf<double> { typedef unsigned long long key; typedef PtF64 point; };
+
+// cell index along one axis: the same expression for binning and for every query
+template <class T> __device__ __forceinline__ int cell_1d(T x, T lo, T h, int dim)
+{
+    const T t = floor((x - lo) / h);
+    // (clamped as a T first: a coordinate far outside the box must not overflow the int conversion)
+    return (int)fmin(fmax(t, (T)0), (T)(dim - 1));
+}
+
+// bounding box of xyz0[0..n0) into g->lo / g->hi (over its finite coordinates) and finite[k] = whether every coordinate of cloud k is
+// finite; the second cloud may be absent (nullptr).  `keys` holds the ordered keys; one round trip, the stream is synchronised.
+template <class T> hipError_t bounds(hipStream_t stream, DevBuf &keys, const T *xyz0, int n0, const T *xyz1, int n1, Grid<T> *g, bool finite[2]);
+
+// counting sort of xyz[0..n) by cell of g (count, scan, scatter): cstart[0 .. cells] = where each cell's points start in `sorted`
+// (GridOf<T>::point, in arbitrary order within a cell); *total = cstart[cells], which is n unless something went wrong.  `cell` and
+// `cursor` are work buffers; the stream is synchronised.
+template <class T> hipError_t build_grid(hipStream_t stream, const T *xyz, int n, const Grid<T> &g, DevBuf &cell, DevBuf &cursor, DevBuf &scan_tmp,
+                                         DevBuf &cstart, DevBuf &sorted, int *total);
+
+// ---- radix select -----------------------------------------------------------------------------------------------------------------------
+// The key of a given rank among the 64-bit keys that `pass` sees, a byte per pass from `shift` down.  pass(prefix, shift, hist) launches
+// one histogram pass on `stream` (bin radix_bin(key, prefix, shift) of every key, added to the 256 device counters at hist);
+// rank_of(total) names the 0-based rank once the first pass has counted the keys.  *rank = the rank that is left among the keys equal
+// to *key, or -1 if a histogram did not hold the rank (an empty set of keys is one way).
+template <class Pass, class RankOf>
+hipError_t select_u64(hipStream_t stream, unsigned *hist, int shift, Pass pass, RankOf rank_of, uint64_t *key, int64_t *rank)
+{
+    uint64_t prefix = 0;
+    *rank = -1;
+    for (bool first = true; shift >= 0; shift -= 8, first = false) {
+        unsigned h[256];
+        BQ_TRY(hipMemsetAsync(hist, 0, sizeof(h), stream));
+        pass(prefix, shift, hist);
+        BQ_TRY(hipGetLastError());
+        BQ_TRY(hipMemcpyAsync(h, hist, sizeof(h), hipMemcpyDeviceToHost, stream));
+        BQ_TRY(hipStreamSynchronize(stream));
+        if (first) *rank = rank_of(std::accumulate(h, h + 256, (int64_t)0));
+        const int b = select_bin(h, *rank);
+        if (b < 0) { *rank = -1; return hipSuccess; }
+        prefix = (prefix << 8) | (uint64_t)b;
+    }
+    *key = prefix;
+    return hipSuccess;
+}
 
 }  // namespace bq

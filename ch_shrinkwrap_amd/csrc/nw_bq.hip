@@ -1,8 +1,14 @@
-// The exclusive scan of the block-boundary query units (nw_bq.h): int, three launches, exact.  It lives in a unit of its own because a
-// __global__ function defined in two units collides at link time through its host stubs.  The per-iteration scan of nanowrap.hip
-// (nw_kernels.h: fused tile sums, recorded in the block's hipGraph) is a different one.
+// The kernels the query units share (nw_bq.h), in a unit of their own because a __global__ function defined in two units collides at
+// link time through its host stubs:
+//   k_bq_scan_*                        the exclusive scan: int, three launches, exact (the per-iteration scan of nanowrap.hip is another one)
+//   k_bq_bbox_*                        bounding box (ordered keys, atomicMin / atomicMax) and finiteness of a cloud
+//   k_bq_cell_count_*, k_bq_scatter_*  counting sort of a cloud by cell of its grid, with the scan between them
+// The grid's kernels are written once as templates over the coordinate type and wrapped in plain kernels _f32 / _f64:
+// build.kernel_resources names a kernel without its template arguments, so two instantiations of one template would share a budget row.
 //
 // All stores are vector stores; no kernel uses scratch (build.py's KERNEL_BUDGETS checks it).
+#include <limits>
+
 #include "nw_bq.h"
 #include "nw_device.h"
 
@@ -71,10 +77,139 @@ __global__ __launch_bounds__(BQ_SCAN_BLOCK) void k_bq_scan_final(const int *__re
 hipError_t bq::scan_exclusive(hipStream_t stream, const int *in, int n, int *out, DevBuf &tmp)
 {
     const int nb = (n + BQ_SCAN_TILE - 1) / BQ_SCAN_TILE;
-    const hipError_t e = tmp.ensure(sizeof(int) * (size_t)(nb + 1));
-    if (e != hipSuccess) return e;
+    BQ_TRY(tmp.ensure(sizeof(int) * (size_t)(nb + 1)));
     hipLaunchKernelGGL(k_bq_scan_tiles, dim3(nb), dim3(BQ_SCAN_BLOCK), 0, stream, in, n, tmp.as<int>());
     hipLaunchKernelGGL(k_bq_scan_bsums, dim3(1), dim3(1024), 0, stream, tmp.as<int>(), nb);
     hipLaunchKernelGGL(k_bq_scan_final, dim3(nb), dim3(BQ_SCAN_BLOCK), 0, stream, in, n, tmp.as<int>(), out);
     return hipGetLastError();
 }
+
+hipError_t bq::scan_total(hipStream_t stream, const int *in, int n, int *out, DevBuf &tmp, int *total)
+{
+    BQ_TRY(scan_exclusive(stream, in, n, out, tmp));
+    BQ_TRY(hipMemcpyAsync(total, out + n, sizeof(int), hipMemcpyDeviceToHost, stream));
+    return hipStreamSynchronize(stream);
+}
+
+// ---- point grid -------------------------------------------------------------------------------------------------------------------------
+#define BQ_BLOCK 256
+
+namespace {
+
+// mm[7]: min xyz, max xyz (ordered keys), non-finite flag
+template <class T> __device__ __forceinline__ void bbox_body(const T *__restrict__ xyz, int n, typename bq::GridOf<T>::key *__restrict__ mm)
+{
+    typedef typename bq::GridOf<T>::key K;
+    K lo[3], hi[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) { lo[d] = std::numeric_limits<K>::max(); hi[d] = std::numeric_limits<K>::min(); }
+    int bad = 0;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            const T x = xyz[3 * (int64_t)i + d];
+            if (!isfinite(x)) { bad = 1; continue; }
+            lo[d] = min(lo[d], bq::enc_ord(x));
+            hi[d] = max(hi[d], bq::enc_ord(x));
+        }
+    }
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { lo[d] = min(lo[d], __shfl_xor(lo[d], o, 64)); hi[d] = max(hi[d], __shfl_xor(hi[d], o, 64)); }
+    }
+    bad = __ballot(bad) != 0;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) { atomicMin(&mm[d], lo[d]); atomicMax(&mm[3 + d], hi[d]); }
+        if (bad) atomicOr(&mm[6], (K)1);
+    }
+}
+
+template <class T> __device__ __forceinline__ void cell_count_body(const T *__restrict__ xyz, int n, const bq::Grid<T> &g, int *__restrict__ cell,
+                                                                   int *__restrict__ count)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const T x = xyz[3 * (int64_t)i], y = xyz[3 * (int64_t)i + 1], z = xyz[3 * (int64_t)i + 2];
+    const int c = (bq::cell_1d(z, g.lo[2], g.h, g.dims[2]) * g.dims[1] + bq::cell_1d(y, g.lo[1], g.h, g.dims[1])) * g.dims[0] + bq::cell_1d(x, g.lo[0], g.h, g.dims[0]);
+    cell[i] = c;
+    atomicAdd(&count[c], 1);
+}
+
+// (the one line that differs between the two scatters)
+__device__ __forceinline__ float4 point_of(const float *p, int) { return make_float4(p[0], p[1], p[2], 0.0f); }
+__device__ __forceinline__ bq::PtF64 point_of(const double *p, int i) { return {p[0], p[1], p[2], i}; }
+
+template <class T> __device__ __forceinline__ void scatter_body(const T *__restrict__ xyz, int n, const int *__restrict__ cell, int *__restrict__ cursor,
+                                                                typename bq::GridOf<T>::point *__restrict__ sorted)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int slot = atomicAdd(&cursor[cell[i]], 1);          // (order inside a cell is arbitrary: no query may depend on it)
+    if (slot < 0 || slot >= n) return;                        // (cannot happen: the cursors start at the scan of the counts)
+    sorted[slot] = point_of(xyz + 3 * (int64_t)i, i);
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(BQ_BLOCK) void k_bq_bbox_f32(const float *__restrict__ xyz, int n, int *__restrict__ mm) { bbox_body(xyz, n, mm); }
+__global__ __launch_bounds__(BQ_BLOCK) void k_bq_bbox_f64(const double *__restrict__ xyz, int n, unsigned long long *__restrict__ mm) { bbox_body(xyz, n, mm); }
+__global__ __launch_bounds__(BQ_BLOCK) void k_bq_cell_count_f32(const float *__restrict__ xyz, int n, bq::Grid<float> g, int *__restrict__ cell, int *__restrict__ count) { cell_count_body(xyz, n, g, cell, count); }
+__global__ __launch_bounds__(BQ_BLOCK) void k_bq_cell_count_f64(const double *__restrict__ xyz, int n, bq::Grid<double> g, int *__restrict__ cell, int *__restrict__ count) { cell_count_body(xyz, n, g, cell, count); }
+__global__ __launch_bounds__(BQ_BLOCK) void k_bq_scatter_f32(const float *__restrict__ xyz, int n, const int *__restrict__ cell, int *__restrict__ cursor, float4 *__restrict__ sorted) { scatter_body(xyz, n, cell, cursor, sorted); }
+__global__ __launch_bounds__(BQ_BLOCK) void k_bq_scatter_f64(const double *__restrict__ xyz, int n, const int *__restrict__ cell, int *__restrict__ cursor, bq::PtF64 *__restrict__ sorted) { scatter_body(xyz, n, cell, cursor, sorted); }
+
+// the kernels of a coordinate type
+static constexpr auto bbox_kernel(const float *) { return k_bq_bbox_f32; }
+static constexpr auto bbox_kernel(const double *) { return k_bq_bbox_f64; }
+static constexpr auto cell_count_kernel(const float *) { return k_bq_cell_count_f32; }
+static constexpr auto cell_count_kernel(const double *) { return k_bq_cell_count_f64; }
+static constexpr auto scatter_kernel(const float *) { return k_bq_scatter_f32; }
+static constexpr auto scatter_kernel(const double *) { return k_bq_scatter_f64; }
+
+template <class T> hipError_t bq::bounds(hipStream_t stream, DevBuf &keys, const T *xyz0, int n0, const T *xyz1, int n1, Grid<T> *g, bool finite[2])
+{
+    typedef typename GridOf<T>::key K;
+    const K top = std::numeric_limits<K>::max(), bottom = std::numeric_limits<K>::min();
+    const K mm0[14] = {top, top, top, bottom, bottom, bottom, 0, top, top, top, bottom, bottom, bottom, 0};
+    K mm[14];
+    BQ_TRY(keys.ensure(sizeof(mm0)));
+    BQ_TRY(hipMemcpyAsync(keys.p, mm0, sizeof(mm0), hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(bbox_kernel(xyz0), dim3(std::min(nblk(n0), 1024)), dim3(BQ_BLOCK), 0, stream, xyz0, n0, keys.as<K>());
+    if (xyz1) hipLaunchKernelGGL(bbox_kernel(xyz1), dim3(std::min(nblk(n1), 1024)), dim3(BQ_BLOCK), 0, stream, xyz1, n1, keys.as<K>() + 7);
+    BQ_TRY(hipGetLastError());
+    BQ_TRY(hipMemcpyAsync(mm, keys.p, sizeof(mm), hipMemcpyDeviceToHost, stream));
+    BQ_TRY(hipStreamSynchronize(stream));
+    for (int d = 0; d < 3; ++d) { g->lo[d] = dec_ord(mm[d]); g->hi[d] = dec_ord(mm[3 + d]); }
+    finite[0] = mm[6] == 0;
+    finite[1] = mm[13] == 0;
+    return hipSuccess;
+}
+
+template <class T> hipError_t bq::build_grid(hipStream_t stream, const T *xyz, int n, const Grid<T> &g, DevBuf &cell, DevBuf &cursor, DevBuf &scan_tmp,
+                                             DevBuf &cstart, DevBuf &sorted, int *total)
+{
+    typedef typename GridOf<T>::point P;
+    const int64_t ncell = g.cells();
+    BQ_TRY(cell.ensure(sizeof(int) * (size_t)n));
+    BQ_TRY(cursor.ensure(sizeof(int) * (size_t)(ncell + 1)));                                    // counts, then the cursors
+    BQ_TRY(cstart.ensure(sizeof(int) * (size_t)(ncell + 1)));
+    BQ_TRY(sorted.ensure(sizeof(P) * (size_t)n));
+    BQ_TRY(hipMemsetAsync(cursor.p, 0, sizeof(int) * (size_t)(ncell + 1), stream));
+    hipLaunchKernelGGL(cell_count_kernel(xyz), dim3(nblk(n)), dim3(BQ_BLOCK), 0, stream, xyz, n, g, cell.as<int>(), cursor.as<int>());
+    BQ_TRY(hipGetLastError());
+    BQ_TRY(scan_exclusive(stream, cursor.as<int>(), (int)ncell, cstart.as<int>(), scan_tmp));
+    BQ_TRY(hipMemcpyAsync(cursor.p, cstart.p, sizeof(int) * (size_t)ncell, hipMemcpyDeviceToDevice, stream));
+    hipLaunchKernelGGL(scatter_kernel(xyz), dim3(nblk(n)), dim3(BQ_BLOCK), 0, stream, xyz, n, cell.as<int>(), cursor.as<int>(), sorted.as<P>());
+    BQ_TRY(hipGetLastError());
+    // (the total is read once the scatter is queued: one wait for both, after which the caller's xyz is no longer read)
+    *total = -1;
+    BQ_TRY(hipMemcpyAsync(total, cstart.as<int>() + ncell, sizeof(int), hipMemcpyDeviceToHost, stream));
+    return hipStreamSynchronize(stream);
+}
+
+template hipError_t bq::bounds<float>(hipStream_t, DevBuf &, const float *, int, const float *, int, Grid<float> *, bool[2]);
+template hipError_t bq::bounds<double>(hipStream_t, DevBuf &, const double *, int, const double *, int, Grid<double> *, bool[2]);
+template hipError_t bq::build_grid<float>(hipStream_t, const float *, int, const Grid<float> &, DevBuf &, DevBuf &, DevBuf &, DevBuf &, DevBuf &, int *);
+template hipError_t bq::build_grid<double>(hipStream_t, const double *, int, const Grid<double> &, DevBuf &, DevBuf &, DevBuf &, DevBuf &, DevBuf &, int *);

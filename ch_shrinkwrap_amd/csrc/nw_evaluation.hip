@@ -10,14 +10,15 @@
 //                   (scan)            output slots
 //                   k_ev_emit         one thread per node inside its triangle: position and face id
 //                   The order is the host function's by construction: nodes are numbered by face, row-major within a face.
-//   nearest         k_ev_bbox         bounding box (ordered 64-bit keys, atomicMin / atomicMax) and finiteness of a cloud
-//                   k_ev_cell_count, (scan), k_ev_scatter   counting sort of the reference cloud by cell
+//   nearest         (bq::bounds, bq::size_grid, bq::build_grid)   the query units' shared point grid in double: bounding box of the
+//                                     reference cloud and finiteness of both, counting sort of the reference cloud by cell
 //                   k_ev_nearest      one thread per query: rings of cells around its own until the ring's lower bound exceeds the best
 //                                     squared distance; (d2, index) compared lexicographically, so the order inside a cell (the scatter's
 //                                     atomics) never shows; the block's sum of dist^2 in a fixed order
 //                   k_ev_sum_final    the blocks' partial sums, one workgroup, a fixed order
 //
-// The scan, the device buffer and the context's scaffolding are the block-boundary units' shared ones (nw_bq.h).
+// The scan, the point grid, the device buffer with its staging and the context's scaffolding are the query units' shared ones (nw_bq.h);
+// what is this unit's own about the grid is its starting cell size and its limits (NWE_GRID_RULE).
 // All stores are vector stores; no kernel uses scratch (build.py's KERNEL_BUDGETS checks it).
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -35,17 +36,6 @@
 #define NWE_FACE_NODE_CLIP (1ll << 31)          // a face's node count enters the 64-bit total clipped to this (> NWE_MAX_NODES)
 
 typedef unsigned long long u64;
-
-struct nwe_grid {
-    double lo[3], hi[3];           // the reference cloud's bounding box
-    double h;
-    int dims[3];
-};
-
-struct ev_pt {                     // a reference point in cell order, with its index in the caller's array
-    double x, y, z;
-    long long i;
-};
 
 // ---- mesh sampling --------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NWE_BLOCK) void k_ev_face_setup(const float *__restrict__ pos, const int *__restrict__ faces, int nf, double dx,
@@ -108,88 +98,21 @@ __global__ __launch_bounds__(NWE_BLOCK) void k_ev_emit(const nwe_face_setup *__r
 }
 
 // ---- nearest neighbour ----------------------------------------------------------------------------------------------------------------
-// monotone double <-> u64 map (atomicMin / atomicMax on doubles)
-__device__ __host__ __forceinline__ u64 ev_enc(double d)
-{
-    const u64 u = __builtin_bit_cast(u64, d);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-
-__device__ __host__ __forceinline__ double ev_dec(u64 e)
-{
-    return __builtin_bit_cast(double, (e >> 63) ? (e ^ 0x8000000000000000ull) : ~e);
-}
-
-__global__ __launch_bounds__(NWE_BLOCK) void k_ev_bbox(const double *__restrict__ xyz, int n, u64 *__restrict__ mm /* [7]: min xyz, max xyz, nonfinite */)
-{
-    u64 lo[3] = {~0ull, ~0ull, ~0ull}, hi[3] = {0ull, 0ull, 0ull};
-    int bad = 0;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            const double x = xyz[3 * (int64_t)i + d];
-            if (!isfinite(x)) { bad = 1; continue; }
-            lo[d] = min(lo[d], ev_enc(x));
-            hi[d] = max(hi[d], ev_enc(x));
-        }
-    }
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { lo[d] = min(lo[d], __shfl_xor(lo[d], o, 64)); hi[d] = max(hi[d], __shfl_xor(hi[d], o, 64)); }
-    }
-    bad = __ballot(bad) != 0;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) { atomicMin(&mm[d], lo[d]); atomicMax(&mm[3 + d], hi[d]); }
-        if (bad) atomicOr(&mm[6], 1ull);
-    }
-}
-
-// cell index: the same double expression for binning and for every query
-__device__ __forceinline__ int ev_cell_1d(double x, double lo, double h, int dim)
-{
-    const double t = floor((x - lo) / h);
-    return (int)fmin(fmax(t, 0.0), (double)(dim - 1));
-}
-
-__global__ __launch_bounds__(NWE_BLOCK) void k_ev_cell_count(const double *__restrict__ xyz, int n, nwe_grid g, int *__restrict__ cell, int *__restrict__ count)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double x = xyz[3 * (int64_t)i], y = xyz[3 * (int64_t)i + 1], z = xyz[3 * (int64_t)i + 2];
-    const int c = (ev_cell_1d(z, g.lo[2], g.h, g.dims[2]) * g.dims[1] + ev_cell_1d(y, g.lo[1], g.h, g.dims[1])) * g.dims[0] + ev_cell_1d(x, g.lo[0], g.h, g.dims[0]);
-    cell[i] = c;
-    atomicAdd(&count[c], 1);
-}
-
-__global__ __launch_bounds__(NWE_BLOCK) void k_ev_scatter(const double *__restrict__ xyz, int n, const int *__restrict__ cell, int *__restrict__ cursor,
-                                                          ev_pt *__restrict__ sorted)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int slot = atomicAdd(&cursor[cell[i]], 1);          // (order inside a cell is arbitrary: the query compares (d2, index))
-    if (slot < 0 || slot >= n) return;                        // (cannot happen: the cursors start at the scan of the counts)
-    ev_pt p;
-    p.x = xyz[3 * (int64_t)i]; p.y = xyz[3 * (int64_t)i + 1]; p.z = xyz[3 * (int64_t)i + 2]; p.i = i;
-    sorted[slot] = p;
-}
-
 // the points of cells [c0, c1] of one row against the query
-__device__ __forceinline__ void ev_scan_cells(const ev_pt *__restrict__ pts, const int *__restrict__ cstart, int c0, int c1, double qx, double qy, double qz,
+__device__ __forceinline__ void ev_scan_cells(const bq::PtF64 *__restrict__ pts, const int *__restrict__ cstart, int c0, int c1, double qx, double qy, double qz,
                                               double &best, long long &best_i)
 {
     const int s = cstart[c0], e = cstart[c1 + 1];
     for (int p = s; p < e; ++p) {
-        const ev_pt r = pts[p];
+        const bq::PtF64 r = pts[p];
         const double ex = r.x - qx, ey = r.y - qy, ez = r.z - qz;
         const double d2 = (ex * ex + ey * ey) + ez * ez;
         if (d2 < best || (d2 == best && r.i < best_i)) { best = d2; best_i = r.i; }
     }
 }
 
-__global__ __launch_bounds__(NWE_BLOCK) void k_ev_nearest(const double *__restrict__ q, int nq, const ev_pt *__restrict__ pts, const int *__restrict__ cstart,
-                                                          nwe_grid g, double *__restrict__ dist, int *__restrict__ idx, double *__restrict__ partial)
+__global__ __launch_bounds__(NWE_BLOCK) void k_ev_nearest(const double *__restrict__ q, int nq, const bq::PtF64 *__restrict__ pts, const int *__restrict__ cstart,
+                                                          bq::Grid<double> g, double *__restrict__ dist, int *__restrict__ idx, double *__restrict__ partial)
 {
     __shared__ double s_w[NWE_BLOCK / 64];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -199,7 +122,7 @@ __global__ __launch_bounds__(NWE_BLOCK) void k_ev_nearest(const double *__restri
         // the query's projection onto the reference cloud's box: every reference point p has |p - q|^2 >= |p - q'|^2 + |q - q'|^2
         const double px = fmin(fmax(qx, g.lo[0]), g.hi[0]), py = fmin(fmax(qy, g.lo[1]), g.hi[1]), pz = fmin(fmax(qz, g.lo[2]), g.hi[2]);
         const double out2 = (((qx - px) * (qx - px) + (qy - py) * (qy - py)) + (qz - pz) * (qz - pz)) * (1.0 - 1e-9);
-        const int cx = ev_cell_1d(px, g.lo[0], g.h, g.dims[0]), cy = ev_cell_1d(py, g.lo[1], g.h, g.dims[1]), cz = ev_cell_1d(pz, g.lo[2], g.h, g.dims[2]);
+        const int cx = bq::cell_1d(px, g.lo[0], g.h, g.dims[0]), cy = bq::cell_1d(py, g.lo[1], g.h, g.dims[1]), cz = bq::cell_1d(pz, g.lo[2], g.h, g.dims[2]);
         const int rmax = max(max(max(cx, g.dims[0] - 1 - cx), max(cy, g.dims[1] - 1 - cy)), max(cz, g.dims[2] - 1 - cz));
         double best = INFINITY;
         long long best_i = LLONG_MAX;
@@ -285,76 +208,38 @@ int resolve(nwe_ctx *ctx, const double *p, int64_t n, DevBuf &stage, const doubl
         *n_out = (int)ctx->n_samples;
         return NWE_OK;
     }
-    hipPointerAttribute_t attr;
-    const bool on_device = hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeDevice;
-    (void)hipGetLastError();                                  // (a host pointer leaves an error behind on some runtimes)
     *n_out = (int)n;
-    if (on_device) { *dev = p; return NWE_OK; }
-    NWE_HIP(stage.ensure(sizeof(double) * 3 * (size_t)n));
-    NWE_HIP(hipMemcpyAsync(stage.p, p, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    if (bq::on_device(p)) { *dev = p; return NWE_OK; }
+    NWE_HIP(bq::upload(ctx->stream, stage, p, 3 * n));
     *dev = stage.as<double>();
     return NWE_OK;
 }
 
-// cell size: about one reference point per cell of the box (the flattest axis counts as a thousandth of the widest), at most 1025 cells
-// an axis, then widened until the grid has at most max(2 n, 65536) cells
-int make_grid(nwe_ctx *ctx, const u64 *mm, int n, nwe_grid *g)
-{
-    double ext[3], emax = 0.0;
-    for (int d = 0; d < 3; ++d) { g->lo[d] = ev_dec(mm[d]); g->hi[d] = ev_dec(mm[3 + d]); ext[d] = g->hi[d] - g->lo[d]; emax = std::max(emax, ext[d]); }
-    if (!std::isfinite(emax)) return fail(ctx, NWE_ERR_BADARG, "nwe_nearest: the reference cloud's extent is not a finite double");
-    double h = 1.0;
-    if (emax > 0.0) {
-        h = std::cbrt(std::max(ext[0], 1e-3 * emax) * std::max(ext[1], 1e-3 * emax) * std::max(ext[2], 1e-3 * emax) / n);
-        h = std::max(h, emax / 1024.0);
-        if (!(h > 0.0) || !std::isfinite(h)) h = emax;
-    }
-    const int64_t cap = std::min<int64_t>(std::max<int64_t>(2ll * n, 65536), 1ll << 28);      // (cell ids and the scan are int)
-    for (int it = 0; it < 400; ++it) {
-        int64_t cells = 1;
-        for (int d = 0; d < 3; ++d) { g->dims[d] = (int)std::min(1025.0, std::floor(ext[d] / h) + 1.0); cells *= g->dims[d]; }
-        if (cells <= cap) break;
-        h *= 1.1;
-    }
-    g->h = h;
-    if ((int64_t)g->dims[0] * g->dims[1] * g->dims[2] > cap) return fail(ctx, NWE_ERR_BADARG, "nwe_nearest: no cell size keeps the grid within its cap");
-    return NWE_OK;
-}
+// at most max(2 n, 65536) cells, up to 2^28; at most 1025 an axis; 400 widening steps
+const bq::GridRule NWE_GRID_RULE = {2, 1ll << 28, 1025, 400};
 
 // both clouds on the device already
 int nearest_dev(nwe_ctx *ctx, const double *dref, int nr, const double *dq, int nq, double *dist_out, int32_t *idx_out, double *sum_out)
 {
-    // bounding box of the reference cloud, finiteness of both
-    NWE_HIP(ctx->mm.ensure(sizeof(u64) * 14));
-    const u64 mm0[14] = {~0ull, ~0ull, ~0ull, 0, 0, 0, 0, ~0ull, ~0ull, ~0ull, 0, 0, 0, 0};
-    NWE_HIP(hipMemcpyAsync(ctx->mm.p, mm0, sizeof(mm0), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_ev_bbox, dim3(std::min(nblk(nr), 1024)), dim3(NWE_BLOCK), 0, ctx->stream, dref, nr, ctx->mm.as<u64>());
-    hipLaunchKernelGGL(k_ev_bbox, dim3(std::min(nblk(nq), 1024)), dim3(NWE_BLOCK), 0, ctx->stream, dq, nq, ctx->mm.as<u64>() + 7);
-    NWE_HIP(hipGetLastError());
-    u64 mm[14];
-    NWE_HIP(hipMemcpyAsync(mm, ctx->mm.p, sizeof(mm), hipMemcpyDeviceToHost, ctx->stream));
-    NWE_HIP(hipStreamSynchronize(ctx->stream));
-    if (mm[6]) return fail(ctx, NWE_ERR_NONFINITE, "nwe_nearest: a reference point is not finite");
-    if (mm[13]) return fail(ctx, NWE_ERR_NONFINITE, "nwe_nearest: a query point is not finite");
-    nwe_grid g;
-    const int r = make_grid(ctx, mm, nr, &g);
-    if (r != NWE_OK) return r;
-    const int64_t ncell = (int64_t)g.dims[0] * g.dims[1] * g.dims[2];
-    // counting sort of the reference cloud by cell
-    NWE_HIP(ctx->cell.ensure(sizeof(int) * (size_t)nr));
-    NWE_HIP(ctx->ccount.ensure(sizeof(int) * (size_t)(ncell + 1)));            // counts, then the cursors
-    NWE_HIP(ctx->cstart.ensure(sizeof(int) * (size_t)(ncell + 1)));
-    NWE_HIP(ctx->sorted.ensure(sizeof(ev_pt) * (size_t)nr));
-    NWE_HIP(hipMemsetAsync(ctx->ccount.p, 0, sizeof(int) * (size_t)(ncell + 1), ctx->stream));
-    hipLaunchKernelGGL(k_ev_cell_count, dim3(nblk(nr)), dim3(NWE_BLOCK), 0, ctx->stream, dref, nr, g, ctx->cell.as<int>(), ctx->ccount.as<int>());
-    NWE_HIP(hipGetLastError());
-    NWE_HIP(bq::scan_exclusive(ctx->stream, ctx->ccount.as<int>(), (int)ncell, ctx->cstart.as<int>(), ctx->scan_tmp));
-    NWE_HIP(hipMemcpyAsync(ctx->ccount.p, ctx->cstart.p, sizeof(int) * (size_t)ncell, hipMemcpyDeviceToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_ev_scatter, dim3(nblk(nr)), dim3(NWE_BLOCK), 0, ctx->stream, dref, nr, ctx->cell.as<int>(), ctx->ccount.as<int>(), ctx->sorted.as<ev_pt>());
-    NWE_HIP(hipGetLastError());
+    bq::Grid<double> g;
+    bool finite[2];
+    NWE_HIP(bq::bounds<double>(ctx->stream, ctx->mm, dref, nr, dq, nq, &g, finite));
+    if (!finite[0]) return fail(ctx, NWE_ERR_NONFINITE, "nwe_nearest: a reference point is not finite");
+    if (!finite[1]) return fail(ctx, NWE_ERR_NONFINITE, "nwe_nearest: a query point is not finite");
+    double ext[3], emax = 0.0;
+    for (int d = 0; d < 3; ++d) { ext[d] = g.hi[d] - g.lo[d]; emax = std::max(emax, ext[d]); }
+    if (!std::isfinite(emax)) return fail(ctx, NWE_ERR_BADARG, "nwe_nearest: the reference cloud's extent is not a finite double");
+    // cell size: about one reference point per cell of the box (the flattest axis counts as a thousandth of the widest), at most 1025
+    // cells an axis (1 for a cloud without extent); then widened until the grid is within NWE_GRID_RULE
+    g.h = 1.0;
+    if (emax > 0.0) {
+        g.h = std::cbrt(std::max(ext[0], 1e-3 * emax) * std::max(ext[1], 1e-3 * emax) * std::max(ext[2], 1e-3 * emax) / nr);
+        g.h = std::max(g.h, emax / 1024.0);
+        if (!(g.h > 0.0) || !std::isfinite(g.h)) g.h = emax;
+    }
+    if (!bq::size_grid(NWE_GRID_RULE, nr, ext, &g.h, g.dims)) return fail(ctx, NWE_ERR_BADARG, "nwe_nearest: no cell size keeps the grid within its cap");
     int total = -1;
-    NWE_HIP(hipMemcpyAsync(&total, ctx->cstart.as<int>() + ncell, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    NWE_HIP(hipStreamSynchronize(ctx->stream));
+    NWE_HIP(bq::build_grid<double>(ctx->stream, dref, nr, g, ctx->cell, ctx->ccount, ctx->scan_tmp, ctx->cstart, ctx->sorted, &total));
     if (total != nr) return fail(ctx, NWE_ERR_HIP, "nwe_nearest: the cell counts do not add up to the reference points");
     // the queries
     const int nb = nblk(nq);
@@ -362,7 +247,7 @@ int nearest_dev(nwe_ctx *ctx, const double *dref, int nr, const double *dq, int 
     if (idx_out) NWE_HIP(ctx->idx.ensure(sizeof(int) * (size_t)nq));
     NWE_HIP(ctx->partial.ensure(sizeof(double) * (size_t)nb));
     NWE_HIP(ctx->sum.ensure(sizeof(double)));
-    hipLaunchKernelGGL(k_ev_nearest, dim3(nb), dim3(NWE_BLOCK), 0, ctx->stream, dq, nq, ctx->sorted.as<ev_pt>(), ctx->cstart.as<int>(), g,
+    hipLaunchKernelGGL(k_ev_nearest, dim3(nb), dim3(NWE_BLOCK), 0, ctx->stream, dq, nq, ctx->sorted.as<bq::PtF64>(), ctx->cstart.as<int>(), g,
                        dist_out ? ctx->dist.as<double>() : nullptr, idx_out ? ctx->idx.as<int>() : nullptr, ctx->partial.as<double>());
     hipLaunchKernelGGL(k_ev_sum_final, dim3(1), dim3(NWE_BLOCK), 0, ctx->stream, ctx->partial.as<double>(), nb, ctx->sum.as<double>());
     NWE_HIP(hipGetLastError());
@@ -394,15 +279,12 @@ NWE_EXPORT int nwe_sample_mesh(nwe_ctx *ctx, const float *pos, int64_t n_vertice
     ctx->n_samples = 0;
     NWE_HIP(hipSetDevice(ctx->device));
     const int nf = (int)n_faces;
-    const size_t bpos = sizeof(float) * 3 * (size_t)n_vertices, bfac = sizeof(int) * 3 * (size_t)nf;
-    NWE_HIP(ctx->mpos.ensure(bpos));
-    NWE_HIP(ctx->mfaces.ensure(bfac));
+    NWE_HIP(bq::upload(ctx->stream, ctx->mpos, pos, 3 * n_vertices));
+    NWE_HIP(bq::upload(ctx->stream, ctx->mfaces, faces, 3 * n_faces));
     NWE_HIP(ctx->setup.ensure(sizeof(nwe_face_setup) * (size_t)nf));
     NWE_HIP(ctx->count.ensure(sizeof(int) * (size_t)nf));
     NWE_HIP(ctx->off.ensure(sizeof(int) * (size_t)(nf + 1)));
     NWE_HIP(ctx->total.ensure(sizeof(u64)));
-    NWE_HIP(hipMemcpyAsync(ctx->mpos.p, pos, bpos, hipMemcpyHostToDevice, ctx->stream));
-    NWE_HIP(hipMemcpyAsync(ctx->mfaces.p, faces, bfac, hipMemcpyHostToDevice, ctx->stream));
     NWE_HIP(hipMemsetAsync(ctx->total.p, 0, sizeof(u64), ctx->stream));
     // pass 1: set-up and node count per face
     hipLaunchKernelGGL(k_ev_face_setup, dim3(nblk(nf)), dim3(NWE_BLOCK), 0, ctx->stream, ctx->mpos.as<float>(), ctx->mfaces.as<int>(), nf, dx,
@@ -421,10 +303,8 @@ NWE_EXPORT int nwe_sample_mesh(nwe_ctx *ctx, const float *pos, int64_t n_vertice
     hipLaunchKernelGGL(k_ev_node_test, dim3(nblk(n_nodes)), dim3(NWE_BLOCK), 0, ctx->stream, ctx->setup.as<nwe_face_setup>(), ctx->off.as<int>(), nf, n_nodes, dx,
                        ctx->flag.as<int>());
     NWE_HIP(hipGetLastError());
-    NWE_HIP(bq::scan_exclusive(ctx->stream, ctx->flag.as<int>(), n_nodes, ctx->slot.as<int>(), ctx->scan_tmp));
     int n = -1;
-    NWE_HIP(hipMemcpyAsync(&n, ctx->slot.as<int>() + n_nodes, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    NWE_HIP(hipStreamSynchronize(ctx->stream));
+    NWE_HIP(bq::scan_total(ctx->stream, ctx->flag.as<int>(), n_nodes, ctx->slot.as<int>(), ctx->scan_tmp, &n));
     if (n < 0 || n > n_nodes) return fail(ctx, NWE_ERR_HIP, "nwe_sample_mesh: the output slots do not add up");
     if (n == 0) return NWE_OK;
     // pass 3: positions and face ids

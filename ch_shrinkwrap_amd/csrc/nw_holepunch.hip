@@ -4,8 +4,9 @@
 //   step 1  which faces have no localization within eps of their centroid      (:877-887, a cKDTree query per face)
 //   step 2  which opposite candidate face is nearest "in mean-normal space"     (membrane_mesh_utils.c:1301-1376, a serial O(C^2) loop)
 //   step 3  is the prism between a pair of faces empty of localizations         (:946-1016, query_ball_point + six half-plane tests)
-// Here they are kernels over one cell grid of the localizations, built once per fit by a counting sort (count, exclusive scan, scatter).
-// The scan, the device buffer and the context's scaffolding are the block-boundary units' shared ones (nw_bq.h).
+// Here they are kernels over one cell grid of the localizations, built once per fit by the query units' shared counting sort
+// (bq::bounds, bq::size_grid, bq::build_grid: nw_bq.h); the device buffer, the staging of host arrays and the context's scaffolding are
+// the shared ones too.  What is this unit's own about the grid is its starting cell size and its limits (NWH_GRID_RULE).
 //
 //   k_hp_empty_faces  one thread per face: the rows of cells that overlap the eps-ball, first localization within eps ends the search
 //                     (unless the nearest distance was asked for);
@@ -20,7 +21,6 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cmath>
-#include <climits>
 #include <string>
 #include <vector>
 #include <algorithm>
@@ -34,67 +34,9 @@
 
 typedef unsigned long long u64;
 
-struct nwh_grid {
-    float lo[3];
-    float h;
-    int dims[3];
-};
-
-// ---- cell index: the same float expression for binning and for every query -------------------------------------------------------
-__device__ __forceinline__ int hp_cell_1d(float x, float lo, float h, int dim)
-{
-    const float t = floorf((x - lo) / h);
-    // (clamped as a float first: a coordinate far outside the box must not overflow the int conversion)
-    return (int)fminf(fmaxf(t, 0.0f), (float)(dim - 1));
-}
-
-__global__ __launch_bounds__(NWH_BLOCK) void k_hp_bbox(const float *__restrict__ xyz, int n, int *__restrict__ mm /* [7]: min xyz, max xyz, nonfinite */)
-{
-    int lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {INT_MIN, INT_MIN, INT_MIN};
-    int bad = 0;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            const float x = xyz[3 * (int64_t)i + d];
-            if (!isfinite(x)) { bad = 1; continue; }
-            lo[d] = min(lo[d], bq::enc_ord(x));
-            hi[d] = max(hi[d], bq::enc_ord(x));
-        }
-    }
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { lo[d] = min(lo[d], __shfl_xor(lo[d], o, 64)); hi[d] = max(hi[d], __shfl_xor(hi[d], o, 64)); }
-    }
-    bad = __ballot(bad) != 0;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) { atomicMin(&mm[d], lo[d]); atomicMax(&mm[3 + d], hi[d]); }
-        if (bad) atomicOr(&mm[6], 1);
-    }
-}
-
-__global__ __launch_bounds__(NWH_BLOCK) void k_hp_cell_count(const float *__restrict__ xyz, int n, nwh_grid g, int *__restrict__ cell, int *__restrict__ count)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float x = xyz[3 * (int64_t)i], y = xyz[3 * (int64_t)i + 1], z = xyz[3 * (int64_t)i + 2];
-    const int c = (hp_cell_1d(z, g.lo[2], g.h, g.dims[2]) * g.dims[1] + hp_cell_1d(y, g.lo[1], g.h, g.dims[1])) * g.dims[0] + hp_cell_1d(x, g.lo[0], g.h, g.dims[0]);
-    cell[i] = c;
-    atomicAdd(&count[c], 1);
-}
-
-__global__ __launch_bounds__(NWH_BLOCK) void k_hp_scatter(const float *__restrict__ xyz, int n, const int *__restrict__ cell, int *__restrict__ cursor, float4 *__restrict__ sorted)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int slot = atomicAdd(&cursor[cell[i]], 1);       // (order inside a cell is arbitrary: every query is an existence / minimum test)
-    sorted[slot] = make_float4(xyz[3 * (int64_t)i], xyz[3 * (int64_t)i + 1], xyz[3 * (int64_t)i + 2], 0.0f);
-}
-
 // ---- step 1: faces with no localization within eps of their centroid ---------------------------------------------------------------
 __global__ __launch_bounds__(NWH_BLOCK) void k_hp_empty_faces(const float *__restrict__ pos, const int *__restrict__ faces, int nf, float eps,
-                                                              const float4 *__restrict__ pts, const int *__restrict__ cstart, nwh_grid g,
+                                                              const float4 *__restrict__ pts, const int *__restrict__ cstart, bq::Grid<float> g,
                                                               unsigned char *__restrict__ far, float *__restrict__ dist)
 {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
@@ -106,9 +48,9 @@ __global__ __launch_bounds__(NWH_BLOCK) void k_hp_empty_faces(const float *__res
     const float cz = ((pos[3 * a + 2] + pos[3 * b + 2]) + pos[3 * c + 2]) / 3.0f;
     const float eps2 = eps * eps;
     const float r = eps * (1.0f + 1e-5f) + 1e-4f;           // (cell range: a little wider than the ball, the test below is the exact one)
-    const int x0 = hp_cell_1d(cx - r, g.lo[0], g.h, g.dims[0]), x1 = hp_cell_1d(cx + r, g.lo[0], g.h, g.dims[0]);
-    const int y0 = hp_cell_1d(cy - r, g.lo[1], g.h, g.dims[1]), y1 = hp_cell_1d(cy + r, g.lo[1], g.h, g.dims[1]);
-    const int z0 = hp_cell_1d(cz - r, g.lo[2], g.h, g.dims[2]), z1 = hp_cell_1d(cz + r, g.lo[2], g.h, g.dims[2]);
+    const int x0 = bq::cell_1d(cx - r, g.lo[0], g.h, g.dims[0]), x1 = bq::cell_1d(cx + r, g.lo[0], g.h, g.dims[0]);
+    const int y0 = bq::cell_1d(cy - r, g.lo[1], g.h, g.dims[1]), y1 = bq::cell_1d(cy + r, g.lo[1], g.h, g.dims[1]);
+    const int z0 = bq::cell_1d(cz - r, g.lo[2], g.h, g.dims[2]), z1 = bq::cell_1d(cz + r, g.lo[2], g.h, g.dims[2]);
     const bool want_dist = dist != nullptr;
     float best = INFINITY;
     bool found = false;
@@ -274,7 +216,7 @@ __device__ __forceinline__ void hp_column_box(const float *t, const float *nr, c
 }
 
 __global__ __launch_bounds__(NWH_BLOCK) void k_hp_prism(const float *__restrict__ tri, const float *__restrict__ nrm, const int *__restrict__ pair_idx, int n,
-                                                        double eps, const float4 *__restrict__ pts, const int *__restrict__ cstart, nwh_grid g,
+                                                        double eps, const float4 *__restrict__ pts, const int *__restrict__ cstart, bq::Grid<float> g,
                                                         unsigned char *__restrict__ empty)
 {
     const int lane = threadIdx.x & 63;
@@ -313,8 +255,8 @@ __global__ __launch_bounds__(NWH_BLOCK) void k_hp_prism(const float *__restrict_
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
         none |= !(box_lo[d] <= box_hi[d]);
-        lo[d] = hp_cell_1d((float)box_lo[d], g.lo[d], g.h, g.dims[d]);
-        hi[d] = hp_cell_1d((float)box_hi[d], g.lo[d], g.h, g.dims[d]);
+        lo[d] = bq::cell_1d((float)box_lo[d], g.lo[d], g.h, g.dims[d]);
+        hi[d] = bq::cell_1d((float)box_hi[d], g.lo[d], g.h, g.dims[d]);
     }
     if (none) {                                               // (the columns do not meet inside the balls: nothing can be a witness)
         if (lane == 0) empty[k] = 1;
@@ -386,8 +328,7 @@ using bq::nblk;
 struct nwh_ctx : bq::Ctx {
     // the grid of the localizations (nwh_set_points)
     int n_points = 0;
-    int64_t n_cells = 0;
-    nwh_grid grid{};
+    bq::Grid<float> grid{};
     DevBuf pts, cstart;
     // per call
     DevBuf a, b, c, d, e, f;
@@ -396,6 +337,9 @@ struct nwh_ctx : bq::Ctx {
 namespace {
 
 #define NWH_HIP(call) BQ_HIP(call, NWH_ERR_NOMEM, NWH_ERR_HIP)
+
+// at most max(4 n, 65536) cells, up to 2^30; at most 2048 an axis; 200 widening steps
+const bq::GridRule NWH_GRID_RULE = {4, 1ll << 30, 2048, 200};
 
 int check_cands(const int32_t *cands, int64_t nc, int64_t nf)
 {
@@ -436,65 +380,30 @@ NWH_EXPORT int nwh_set_points(nwh_ctx *ctx, const float *xyz, int64_t n_points, 
     const int n = (int)n_points;
     ctx->n_points = 0;
     // a device pointer is read in place, a host one is copied first
-    hipPointerAttribute_t attr;
-    const bool on_device = hipPointerGetAttributes(&attr, xyz) == hipSuccess && attr.type == hipMemoryTypeDevice;
-    (void)hipGetLastError();                                  // (a host pointer leaves an error behind on some runtimes)
     const float *src = xyz;
-    if (!on_device) {
-        NWH_HIP(ctx->a.ensure(sizeof(float) * 3 * (size_t)n));
-        NWH_HIP(hipMemcpyAsync(ctx->a.p, xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    if (!bq::on_device(xyz)) {
+        NWH_HIP(bq::upload(ctx->stream, ctx->a, xyz, 3 * (int64_t)n));
         src = ctx->a.as<float>();
     }
-    // bounding box and finiteness
-    NWH_HIP(ctx->b.ensure(sizeof(int) * 8));
-    const int mm0[8] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN, 0, 0};
-    NWH_HIP(hipMemcpyAsync(ctx->b.p, mm0, sizeof(mm0), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_hp_bbox, dim3(std::min(nblk(n), 1024)), dim3(NWH_BLOCK), 0, ctx->stream, src, n, ctx->b.as<int>());
-    NWH_HIP(hipGetLastError());
-    int mm[8];
-    NWH_HIP(hipMemcpyAsync(mm, ctx->b.p, sizeof(mm), hipMemcpyDeviceToHost, ctx->stream));
-    NWH_HIP(hipStreamSynchronize(ctx->stream));
-    if (mm[6]) return fail(ctx, NWH_ERR_NONFINITE, "nwh_set_points: a localization is not finite");
-    float lo[3], ext[3];
+    bq::Grid<float> g;
+    bool finite[2];
+    NWH_HIP(bq::bounds<float>(ctx->stream, ctx->b, src, n, nullptr, 0, &g, finite));
+    if (!finite[0]) return fail(ctx, NWH_ERR_NONFINITE, "nwh_set_points: a localization is not finite");
+    double ext[3];                                            // (float differences)
     float emax = 0.0f;
-    for (int d = 0; d < 3; ++d) { lo[d] = bq::dec_ord(mm[d]); ext[d] = bq::dec_ord(mm[3 + d]) - lo[d]; emax = std::max(emax, ext[d]); }
+    for (int d = 0; d < 3; ++d) { const float e = g.hi[d] - g.lo[d]; ext[d] = e; emax = std::max(emax, e); }
     emax = std::max(emax, 1e-3f);
-    // cell size: about one localization per cell of the box (the flattest axis counts as a thousandth of the widest), then widened until the
-    // grid has at most max(4 n, 65536) cells and no axis more than 2048
+    // cell size: the caller's, or about one localization per cell of the box (the flattest axis counts as a thousandth of the widest);
+    // then widened until the grid is within NWH_GRID_RULE
     double h = cell_size > 0 ? (double)cell_size
-                             : std::cbrt(std::max((double)ext[0], 1e-3 * emax) * std::max((double)ext[1], 1e-3 * emax) * std::max((double)ext[2], 1e-3 * emax) / n);
+                             : std::cbrt(std::max(ext[0], 1e-3 * emax) * std::max(ext[1], 1e-3 * emax) * std::max(ext[2], 1e-3 * emax) / n);
     h = std::max(h, (double)emax / 2048.0);
-    const int64_t cap = std::min<int64_t>(std::max<int64_t>(4ll * n, 65536), 1ll << 30);     // (cell ids and the scan are int)
-    int dims[3];
-    for (int it = 0; it < 200; ++it) {
-        int64_t cells = 1;
-        for (int d = 0; d < 3; ++d) { dims[d] = (int)std::min<double>(2048.0, std::floor(ext[d] / h) + 1.0); cells *= dims[d]; }
-        if (cells <= cap) break;
-        h *= 1.1;
-    }
-    nwh_grid g;
-    for (int d = 0; d < 3; ++d) { g.lo[d] = lo[d]; g.dims[d] = dims[d]; }
+    if (!bq::size_grid(NWH_GRID_RULE, n, ext, &h, g.dims)) return fail(ctx, NWH_ERR_BADARG, "nwh_set_points: no cell size keeps the grid within its cap");
     g.h = (float)h;
-    const int64_t ncell = (int64_t)dims[0] * dims[1] * dims[2];
-    if (ncell > cap) return fail(ctx, NWH_ERR_BADARG, "nwh_set_points: no cell size keeps the grid within its cap");
-    // counting sort by cell
-    NWH_HIP(ctx->c.ensure(sizeof(int) * (size_t)n));                       // cell of each localization
-    NWH_HIP(ctx->d.ensure(sizeof(int) * (size_t)(ncell + 1)));             // counts, then the cursors
-    NWH_HIP(ctx->cstart.ensure(sizeof(int) * (size_t)(ncell + 1)));
-    NWH_HIP(ctx->pts.ensure(sizeof(float4) * (size_t)n));
-    NWH_HIP(hipMemsetAsync(ctx->d.p, 0, sizeof(int) * (size_t)(ncell + 1), ctx->stream));
-    hipLaunchKernelGGL(k_hp_cell_count, dim3(nblk(n)), dim3(NWH_BLOCK), 0, ctx->stream, src, n, g, ctx->c.as<int>(), ctx->d.as<int>());
-    NWH_HIP(hipGetLastError());
-    NWH_HIP(bq::scan_exclusive(ctx->stream, ctx->d.as<int>(), (int)ncell, ctx->cstart.as<int>(), ctx->e));
-    NWH_HIP(hipMemcpyAsync(ctx->d.p, ctx->cstart.p, sizeof(int) * (size_t)ncell, hipMemcpyDeviceToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_hp_scatter, dim3(nblk(n)), dim3(NWH_BLOCK), 0, ctx->stream, src, n, ctx->c.as<int>(), ctx->d.as<int>(), ctx->pts.as<float4>());
-    NWH_HIP(hipGetLastError());
     int total = -1;
-    NWH_HIP(hipMemcpyAsync(&total, ctx->cstart.as<int>() + ncell, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    NWH_HIP(hipStreamSynchronize(ctx->stream));
+    NWH_HIP(bq::build_grid<float>(ctx->stream, src, n, g, ctx->c, ctx->d, ctx->e, ctx->cstart, ctx->pts, &total));
     if (total != n) return fail(ctx, NWH_ERR_HIP, "nwh_set_points: the cell counts do not add up to the localizations");
     ctx->grid = g;
-    ctx->n_cells = ncell;
     ctx->n_points = n;
     return NWH_OK;
 }
@@ -508,13 +417,10 @@ NWH_EXPORT int nwh_empty_faces(nwh_ctx *ctx, const float *pos, int64_t n_vertice
     if (ctx->n_points < 1) return fail(ctx, NWH_ERR_NOPOINTS, "nwh_empty_faces: nwh_set_points first");
     NWH_HIP(hipSetDevice(ctx->device));
     const int nf = (int)n_faces;
-    const size_t bpos = sizeof(float) * 3 * (size_t)n_vertices, bfac = sizeof(int) * 3 * (size_t)nf;
-    NWH_HIP(ctx->a.ensure(bpos));
-    NWH_HIP(ctx->b.ensure(bfac));
+    NWH_HIP(bq::upload(ctx->stream, ctx->a, pos, 3 * n_vertices));
+    NWH_HIP(bq::upload(ctx->stream, ctx->b, faces, 3 * n_faces));
     NWH_HIP(ctx->c.ensure((size_t)nf));
     if (dist) NWH_HIP(ctx->f.ensure(sizeof(float) * (size_t)nf));
-    NWH_HIP(hipMemcpyAsync(ctx->a.p, pos, bpos, hipMemcpyHostToDevice, ctx->stream));
-    NWH_HIP(hipMemcpyAsync(ctx->b.p, faces, bfac, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_hp_empty_faces, dim3(nblk(nf)), dim3(NWH_BLOCK), 0, ctx->stream, ctx->a.as<float>(), ctx->b.as<int>(), nf, eps,
                        ctx->pts.as<float4>(), ctx->cstart.as<int>(), ctx->grid, ctx->c.as<unsigned char>(), dist ? ctx->f.as<float>() : nullptr);
     NWH_HIP(hipGetLastError());
@@ -536,14 +442,12 @@ NWH_EXPORT int nwh_pair_faces(nwh_ctx *ctx, const float *pos, int64_t n_vertices
     const int nc = (int)n_cands;
     std::vector<float> tri, nrm;
     gather(pos, faces, face_normals, cands, nc, tri, nrm);
-    NWH_HIP(ctx->a.ensure(sizeof(float) * tri.size()));
-    NWH_HIP(ctx->b.ensure(sizeof(float) * nrm.size()));
+    NWH_HIP(bq::upload(ctx->stream, ctx->a, tri.data(), (int64_t)tri.size()));
+    NWH_HIP(bq::upload(ctx->stream, ctx->b, nrm.data(), (int64_t)nrm.size()));
     NWH_HIP(ctx->c.ensure(sizeof(float4) * (size_t)nc));
     NWH_HIP(ctx->d.ensure(sizeof(float4) * (size_t)nc));
     NWH_HIP(ctx->e.ensure(sizeof(u64) * (size_t)nc));
     NWH_HIP(ctx->f.ensure(sizeof(int) * (size_t)nc));
-    NWH_HIP(hipMemcpyAsync(ctx->a.p, tri.data(), sizeof(float) * tri.size(), hipMemcpyHostToDevice, ctx->stream));
-    NWH_HIP(hipMemcpyAsync(ctx->b.p, nrm.data(), sizeof(float) * nrm.size(), hipMemcpyHostToDevice, ctx->stream));
     NWH_HIP(hipMemsetAsync(ctx->e.p, 0xff, sizeof(u64) * (size_t)nc, ctx->stream));
     hipLaunchKernelGGL(k_hp_cand_geom, dim3(nblk(nc)), dim3(NWH_BLOCK), 0, ctx->stream, ctx->a.as<float>(), ctx->b.as<float>(), nc, ctx->c.as<float4>(), ctx->d.as<float4>());
     const dim3 grid(nblk(nc), (unsigned)((nc + NWH_PAIR_CHUNK - 1) / NWH_PAIR_CHUNK));
@@ -570,13 +474,10 @@ NWH_EXPORT int nwh_prism_empty(nwh_ctx *ctx, const float *pos, int64_t n_vertice
     const int nc = (int)n;
     std::vector<float> tri, nrm;
     gather(pos, faces, face_normals, cands, nc, tri, nrm);
-    NWH_HIP(ctx->a.ensure(sizeof(float) * tri.size()));
-    NWH_HIP(ctx->b.ensure(sizeof(float) * nrm.size()));
-    NWH_HIP(ctx->c.ensure(sizeof(int) * (size_t)nc));
+    NWH_HIP(bq::upload(ctx->stream, ctx->a, tri.data(), (int64_t)tri.size()));
+    NWH_HIP(bq::upload(ctx->stream, ctx->b, nrm.data(), (int64_t)nrm.size()));
+    NWH_HIP(bq::upload(ctx->stream, ctx->c, pair_idx, n));
     NWH_HIP(ctx->f.ensure((size_t)nc));
-    NWH_HIP(hipMemcpyAsync(ctx->a.p, tri.data(), sizeof(float) * tri.size(), hipMemcpyHostToDevice, ctx->stream));
-    NWH_HIP(hipMemcpyAsync(ctx->b.p, nrm.data(), sizeof(float) * nrm.size(), hipMemcpyHostToDevice, ctx->stream));
-    NWH_HIP(hipMemcpyAsync(ctx->c.p, pair_idx, sizeof(int) * (size_t)nc, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_hp_prism, dim3(nblk(nc, NWH_BLOCK / 64)), dim3(NWH_BLOCK), 0, ctx->stream, ctx->a.as<float>(), ctx->b.as<float>(), ctx->c.as<int>(), nc,
                        (double)eps, ctx->pts.as<float4>(), ctx->cstart.as<int>(), ctx->grid, ctx->f.as<unsigned char>());
     NWH_HIP(hipGetLastError());

@@ -2,8 +2,8 @@
 //
 // The start surface of a fit, made from the cloud itself: count per voxel, integer binomial smoothing, a threshold from the median of the
 // occupied voxels, and sheet-aware surface nets of `field > thr`.  The definitions are the header's; the NumPy restatement the kernels are
-// tested against is tests/isosurface_ref.py.  The scan, the device buffer and the context's scaffolding are the block-boundary units'
-// shared ones (nw_bq.h).
+// tested against is tests/isosurface_ref.py.  The scan, the host loop and the bin rule of the radix select, the device buffer with its
+// staging and the context's scaffolding are the query units' shared ones (nw_bq.h).
 //
 //   k_iso_count        one localization per thread, four per thread and workgroup pass: voxel ids are aggregated in an LDS hash table
 //                      (2048 slots, four probes) and flushed with one global atomic per slot; what finds no slot goes to HBM directly.
@@ -117,9 +117,8 @@ __global__ __launch_bounds__(NWI_BLOCK) void k_iso_hist(const u64 *__restrict__ 
     __syncthreads();
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         if (count[i] == 0u) continue;
-        const u64 f = field[i];
-        const u64 hi = shift >= 56 ? 0ull : f >> (shift + 8);
-        if (hi == prefix) atomicAdd(&s_h[(unsigned)(f >> shift) & 255u], 1u);
+        const int b = bq::radix_bin(field[i], prefix, shift);
+        if (b >= 0) atomicAdd(&s_h[b], 1u);
     }
     __syncthreads();
     const unsigned c = s_h[threadIdx.x];
@@ -322,8 +321,7 @@ NWI_EXPORT int nwi_set_sheet_table(nwi_ctx *ctx, const int8_t *table)
     if (!ctx) return NWI_ERR_BADARG;
     NWI_HIP(hipSetDevice(ctx->device));
     ctx->have_table = false;
-    NWI_HIP(ctx->tab16.ensure(t16.size()));
-    NWI_HIP(hipMemcpyAsync(ctx->tab16.p, t16.data(), t16.size(), hipMemcpyHostToDevice, ctx->stream));
+    NWI_HIP(bq::upload(ctx->stream, ctx->tab16, t16.data(), (int64_t)t16.size()));
     NWI_HIP(hipStreamSynchronize(ctx->stream));                 // (t16 is a local)
     ctx->have_table = true;
     return NWI_OK;
@@ -361,8 +359,7 @@ NWI_EXPORT int nwi_density(nwi_ctx *ctx, const float *xyz, int64_t n_points, int
     ctx->n_vertices = ctx->n_faces = -1;
     const float *src = xyz;
     if (!points_on_device) {
-        NWI_HIP(ctx->pts.ensure(sizeof(float) * 3 * (size_t)n));
-        NWI_HIP(hipMemcpyAsync(ctx->pts.p, xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+        NWI_HIP(bq::upload(ctx->stream, ctx->pts, xyz, 3 * n_points));
         src = ctx->pts.as<float>();
     }
     NWI_HIP(ctx->counts.ensure(sizeof(unsigned) * (size_t)nv));
@@ -408,27 +405,18 @@ NWI_EXPORT int nwi_threshold_auto(nwi_ctx *ctx, double fraction, uint64_t *media
     const u64 vmax = (u64)ctx->n_points << (6 * ctx->passes);
     int shift = 56;
     while (shift > 0 && (vmax >> shift) == 0ull) shift -= 8;
-    u64 prefix = 0ull;
+    // the lower median of the occupied voxels' field values (the first pass sees every occupied voxel)
     int64_t rank = -1, occupied = 0;
-    unsigned *hist = ctx->small.as<unsigned>() + 256;           // (small[0] is the counting kernel's flag word)
-    for (; shift >= 0; shift -= 8) {
-        NWI_HIP(hipMemsetAsync(hist, 0, sizeof(unsigned) * 256, ctx->stream));
+    uint64_t prefix = 0;
+    const auto pass = [&](uint64_t pre, int sh, unsigned *hist) {
         hipLaunchKernelGGL(k_iso_hist, dim3(std::min(nblk(ctx->n_vox), 2048)), dim3(NWI_BLOCK), 0, ctx->stream, ctx->field, ctx->counts.as<unsigned>(),
-                           ctx->n_vox, prefix, shift, hist);
-        NWI_HIP(hipGetLastError());
-        unsigned h[256];
-        NWI_HIP(hipMemcpyAsync(h, hist, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-        NWI_HIP(hipStreamSynchronize(ctx->stream));
-        if (rank < 0) {                                         // the first pass sees every occupied voxel
-            for (int b = 0; b < 256; ++b) occupied += h[b];
-            if (occupied == 0) return fail(ctx, NWI_ERR_EMPTY, "nwi_threshold_auto: no occupied voxel");
-            rank = (occupied - 1) / 2;
-        }
-        int b = 0;
-        for (; b < 255 && rank >= (int64_t)h[b]; ++b) rank -= h[b];
-        if (rank >= (int64_t)h[b]) return fail(ctx, NWI_ERR_HIP, "nwi_threshold_auto: the histogram does not hold the rank");
-        prefix = (prefix << 8) | (u64)b;
-    }
+                           ctx->n_vox, (u64)pre, sh, hist);
+    };
+    const auto lower_median = [&](int64_t total) { occupied = total; return (total - 1) / 2; };
+    unsigned *bins = ctx->small.as<unsigned>() + 256;           // (small[0] is the counting kernel's flag word)
+    NWI_HIP(bq::select_u64(ctx->stream, bins, shift, pass, lower_median, &prefix, &rank));
+    if (occupied == 0) return fail(ctx, NWI_ERR_EMPTY, "nwi_threshold_auto: no occupied voxel");
+    if (rank < 0) return fail(ctx, NWI_ERR_HIP, "nwi_threshold_auto: the histogram does not hold the rank");
     const double t = std::floor(fraction * (double)prefix);
     if (!(t < 18446744073709551616.0)) return fail(ctx, NWI_ERR_BADARG, "nwi_threshold_auto: fraction * median does not fit the field");
     *thr = (u64)t;
@@ -457,11 +445,9 @@ NWI_EXPORT int nwi_extract(nwi_ctx *ctx, uint64_t thr, int64_t *n_vertices, int6
     hipLaunchKernelGGL(k_iso_pattern, dim3(nblk(ncell)), dim3(NWI_BLOCK), 0, ctx->stream, ctx->field, (u64)thr, nx, ny, nz, ctx->cfg.as<unsigned char>(),
                        ctx->act.as<int>(), flags);
     NWI_HIP(hipGetLastError());
-    NWI_HIP(bq::scan_exclusive(ctx->stream, ctx->act.as<int>(), ncell, ctx->scan.as<int>(), ctx->scan_tmp));
     int na = 0, fl = 0;
-    NWI_HIP(hipMemcpyAsync(&na, ctx->scan.as<int>() + ncell, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    NWI_HIP(hipMemcpyAsync(&fl, flags, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    NWI_HIP(hipStreamSynchronize(ctx->stream));
+    NWI_HIP(hipMemcpyAsync(&fl, flags, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));         // (arrives with the scan's total)
+    NWI_HIP(bq::scan_total(ctx->stream, ctx->act.as<int>(), ncell, ctx->scan.as<int>(), ctx->scan_tmp, &na));
     if (fl & 1) return fail(ctx, NWI_ERR_BORDER, "nwi_extract: an inside node on the outermost layer of the grid (pad the grid)");
     if (na < 1) return fail(ctx, NWI_ERR_EMPTY, "nwi_extract: no lattice edge crosses the threshold");
     if (na > NWI_MAX_ACTIVE) return fail(ctx, NWI_ERR_BADARG, "nwi_extract: more than 2^29 surface cells");
@@ -474,12 +460,9 @@ NWI_EXPORT int nwi_extract(nwi_ctx *ctx, uint64_t thr, int64_t *n_vertices, int6
     hipLaunchKernelGGL(k_iso_cell_counts, dim3(nblk(na)), dim3(NWI_BLOCK), 0, ctx->stream, ctx->alist.as<int>(), na, ctx->cfg.as<unsigned char>(),
                        ctx->tab16.as<unsigned char>(), ctx->vcnt.as<int>(), ctx->qflag.as<int>());
     NWI_HIP(hipGetLastError());
-    NWI_HIP(bq::scan_exclusive(ctx->stream, ctx->vcnt.as<int>(), na, ctx->voff.as<int>(), ctx->scan_tmp));
-    NWI_HIP(bq::scan_exclusive(ctx->stream, ctx->qflag.as<int>(), 3 * na, ctx->qoff.as<int>(), ctx->scan_tmp));
     int nv = 0, nq = 0;
-    NWI_HIP(hipMemcpyAsync(&nv, ctx->voff.as<int>() + na, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    NWI_HIP(hipMemcpyAsync(&nq, ctx->qoff.as<int>() + 3 * (size_t)na, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    NWI_HIP(hipStreamSynchronize(ctx->stream));
+    NWI_HIP(bq::scan_total(ctx->stream, ctx->vcnt.as<int>(), na, ctx->voff.as<int>(), ctx->scan_tmp, &nv));
+    NWI_HIP(bq::scan_total(ctx->stream, ctx->qflag.as<int>(), 3 * na, ctx->qoff.as<int>(), ctx->scan_tmp, &nq));
     if (nv < 1 || nq < 1 || nv > 4 * (int64_t)na || nq > 3 * (int64_t)na) return fail(ctx, NWI_ERR_HIP, "nwi_extract: the counts of the surface cells do not add up");
     NWI_HIP(ctx->verts.ensure(sizeof(float) * 3 * (size_t)nv));
     NWI_HIP(ctx->keys.ensure(sizeof(long long) * (size_t)nv));

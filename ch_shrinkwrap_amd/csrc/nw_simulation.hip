@@ -19,7 +19,8 @@
 //   clusters        k_sim_copy_hist     radix select of the sz-th smallest copy key, a byte per pass; the keys are recomputed, never stored
 //                   k_sim_copy_equal, (scan), k_sim_copy_keep, (scan), k_sim_copy_emit
 //
-// The scan, the device buffer and the context's scaffolding are the block-boundary units' shared ones (nw_bq.h).
+// The scan, the host loop and the bin rule of the radix select, the device buffer with its staging, the finiteness check of a host array
+// and the context's scaffolding are the query units' shared ones (nw_bq.h).
 // All stores are vector stores; no kernel uses scratch (build.py's KERNEL_BUDGETS checks it).
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -342,8 +343,8 @@ __global__ __launch_bounds__(NWG_BLOCK) void k_sim_copy_hist(int n_copies, u64 s
     s_h[threadIdx.x] = 0u;
     __syncthreads();
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n_copies; j += gridDim.x * blockDim.x) {
-        const u64 key = sim_key64((u64)j, stream, seed);
-        if (shift == 56 || (key >> (shift + 8)) == prefix) atomicAdd(&s_h[(key >> shift) & 255u], 1u);
+        const int b = bq::radix_bin(sim_key64((u64)j, stream, seed), prefix, shift);
+        if (b >= 0) atomicAdd(&s_h[b], 1u);
     }
     __syncthreads();
     if (s_h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], s_h[threadIdx.x]);
@@ -405,13 +406,6 @@ struct nwg_ctx : bq::Ctx {
 namespace {
 
 #define NWG_HIP(call) BQ_HIP(call, NWG_ERR_NOMEM, NWG_ERR_HIP)
-
-bool finite_array(const double *p, int64_t n)
-{
-    for (int64_t i = 0; i < n; ++i)
-        if (!std::isfinite(p[i])) return false;
-    return true;
-}
 
 bool count_ok(int64_t n) { return n >= 1 && n <= (1ll << 30); }
 
@@ -478,13 +472,6 @@ void morton_cells(int x, int y, int z, int bits, int lo, int hi, std::vector<int
     for (int k = 0; k < 8; ++k) morton_cells(x + (k & 1) * h, y + ((k >> 1) & 1) * h, z + (k >> 2) * h, bits - 1, lo, hi, out);
 }
 
-int upload(nwg_ctx *ctx, DevBuf &buf, const void *src, size_t bytes)
-{
-    NWG_HIP(buf.ensure(bytes));
-    NWG_HIP(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return NWG_OK;
-}
-
 }  // namespace
 
 NWG_EXPORT int nwg_abi_version(void) { return NWG_ABI_VERSION; }
@@ -503,8 +490,7 @@ NWG_EXPORT int nwg_set_program(nwg_ctx *ctx, const nwg_op *ops, int n_ops)
     if (!ctx) return NWG_ERR_BADARG;
     ctx->n_ops = 0;
     NWG_HIP(hipSetDevice(ctx->device));
-    const int r = upload(ctx, ctx->prog, ops, sizeof(nwg_op) * (size_t)n_ops);
-    if (r != NWG_OK) return r;
+    NWG_HIP(bq::upload(ctx->stream, ctx->prog, ops, n_ops));
     NWG_HIP(hipStreamSynchronize(ctx->stream));
     ctx->n_ops = n_ops;
     return NWG_OK;
@@ -515,10 +501,9 @@ NWG_EXPORT int nwg_eval(nwg_ctx *ctx, const double *xyz, int64_t n, double *d_ou
     if (!xyz || !d_out || !count_ok(n)) return NWG_ERR_BADARG;
     if (!ctx) return NWG_ERR_BADARG;
     if (!ctx->n_ops) return fail(ctx, NWG_ERR_NOPROGRAM, "nwg_eval: no program is set");
-    if (!finite_array(xyz, 3 * n)) return fail(ctx, NWG_ERR_NONFINITE, "nwg_eval: a coordinate is not finite");
+    if (!bq::all_finite(xyz, 3 * n)) return fail(ctx, NWG_ERR_NONFINITE, "nwg_eval: a coordinate is not finite");
     NWG_HIP(hipSetDevice(ctx->device));
-    const int r = upload(ctx, ctx->in0, xyz, sizeof(double) * 3 * (size_t)n);
-    if (r != NWG_OK) return r;
+    NWG_HIP(bq::upload(ctx->stream, ctx->in0, xyz, 3 * n));
     NWG_HIP(ctx->out0.ensure(sizeof(double) * (size_t)n));
     hipLaunchKernelGGL(k_sim_eval, dim3(nblk(n)), dim3(NWG_BLOCK), 0, ctx->stream, ctx->prog.as<nwg_op>(), ctx->n_ops, ctx->in0.as<double>(), (int)n,
                        ctx->out0.as<double>());
@@ -533,10 +518,9 @@ NWG_EXPORT int nwg_normals(nwg_ctx *ctx, const double *xyz, int64_t n, double *n
     if (!xyz || !normals_out || !count_ok(n)) return NWG_ERR_BADARG;
     if (!ctx) return NWG_ERR_BADARG;
     if (!ctx->n_ops) return fail(ctx, NWG_ERR_NOPROGRAM, "nwg_normals: no program is set");
-    if (!finite_array(xyz, 3 * n)) return fail(ctx, NWG_ERR_NONFINITE, "nwg_normals: a coordinate is not finite");
+    if (!bq::all_finite(xyz, 3 * n)) return fail(ctx, NWG_ERR_NONFINITE, "nwg_normals: a coordinate is not finite");
     NWG_HIP(hipSetDevice(ctx->device));
-    const int r = upload(ctx, ctx->in0, xyz, sizeof(double) * 3 * (size_t)n);
-    if (r != NWG_OK) return r;
+    NWG_HIP(bq::upload(ctx->stream, ctx->in0, xyz, 3 * n));
     NWG_HIP(ctx->out0.ensure(sizeof(double) * 3 * (size_t)n));
     hipLaunchKernelGGL(k_sim_normals, dim3(nblk(n)), dim3(NWG_BLOCK), 0, ctx->stream, ctx->prog.as<nwg_op>(), ctx->n_ops, ctx->in0.as<double>(), (int)n,
                        ctx->out0.as<double>());
@@ -551,7 +535,7 @@ NWG_EXPORT int nwg_sample_surface(nwg_ctx *ctx, const double *centre, double r_m
 {
     if (!centre || !n_out || !(dx > 0.0) || !std::isfinite(dx) || !(r_max > 0.0) || !std::isfinite(r_max) || !(p >= 0.0) || !std::isfinite(p)) return NWG_ERR_BADARG;
     if (!(lipschitz >= 1.0) || !std::isfinite(lipschitz) || project < 0 || project > 64 || max_points < 1 || max_points > (1ll << 30)) return NWG_ERR_BADARG;
-    if (start_level < -1 || start_level >= NWG_COORD_BITS || !finite_array(centre, 3)) return NWG_ERR_BADARG;
+    if (start_level < -1 || start_level >= NWG_COORD_BITS || !bq::all_finite(centre, 3)) return NWG_ERR_BADARG;
     const double half_nodes = std::floor(r_max / dx);
     if (!(half_nodes <= (double)(NWG_BIAS - 1))) return NWG_ERR_BADARG;          // the node coordinates would not fit NWG_COORD_BITS
     if (!ctx) return NWG_ERR_BADARG;
@@ -578,8 +562,7 @@ NWG_EXPORT int nwg_sample_surface(nwg_ctx *ctx, const double *centre, double r_m
     morton_cells(base, base, base, bits, c0, c1, start);
     NWG_HIP(hipSetDevice(ctx->device));
     int n = (int)(start.size() / 3);
-    int r = upload(ctx, ctx->cells0, start.data(), sizeof(int) * start.size());
-    if (r != NWG_OK) return r;
+    NWG_HIP(bq::upload(ctx->stream, ctx->cells0, start.data(), (int64_t)start.size()));
     NWG_HIP(hipStreamSynchronize(ctx->stream));               // (`start` leaves scope below)
     DevBuf *cur = &ctx->cells0, *nxt = &ctx->cells1;
     const nwg_op *prog = ctx->prog.as<nwg_op>();
@@ -590,10 +573,8 @@ NWG_EXPORT int nwg_sample_surface(nwg_ctx *ctx, const double *centre, double r_m
         NWG_HIP(ctx->slot.ensure(sizeof(int) * ((size_t)n + 1)));
         hipLaunchKernelGGL(k_sim_cell_test, dim3(nblk(n)), dim3(NWG_BLOCK), 0, ctx->stream, prog, ctx->n_ops, cur->as<int>(), n, level, g, bound, ctx->flag.as<int>());
         NWG_HIP(hipGetLastError());
-        NWG_HIP(bq::scan_exclusive(ctx->stream, ctx->flag.as<int>(), n, ctx->slot.as<int>(), ctx->scan_tmp));
         int kept = -1;
-        NWG_HIP(hipMemcpyAsync(&kept, ctx->slot.as<int>() + n, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        NWG_HIP(hipStreamSynchronize(ctx->stream));
+        NWG_HIP(bq::scan_total(ctx->stream, ctx->flag.as<int>(), n, ctx->slot.as<int>(), ctx->scan_tmp, &kept));
         if (kept < 0 || kept > n) return fail(ctx, NWG_ERR_HIP, "nwg_sample_surface: the cell slots do not add up");
         if (kept == 0) return NWG_OK;
         if (8ll * kept > NWG_MAX_CELLS) return fail(ctx, NWG_ERR_TOOMANY, "nwg_sample_surface: " + std::to_string(8ll * kept) + " cells at level " + std::to_string(level - 1));
@@ -609,10 +590,8 @@ NWG_EXPORT int nwg_sample_surface(nwg_ctx *ctx, const double *centre, double r_m
     NWG_HIP(ctx->slot.ensure(sizeof(int) * ((size_t)n + 1)));
     hipLaunchKernelGGL(k_sim_leaf_test, dim3(nblk(n)), dim3(NWG_BLOCK), 0, ctx->stream, prog, ctx->n_ops, cur->as<int>(), n, g, p, (u64)seed, ctx->flag.as<int>());
     NWG_HIP(hipGetLastError());
-    NWG_HIP(bq::scan_exclusive(ctx->stream, ctx->flag.as<int>(), n, ctx->slot.as<int>(), ctx->scan_tmp));
     int found = -1;
-    NWG_HIP(hipMemcpyAsync(&found, ctx->slot.as<int>() + n, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    NWG_HIP(hipStreamSynchronize(ctx->stream));
+    NWG_HIP(bq::scan_total(ctx->stream, ctx->flag.as<int>(), n, ctx->slot.as<int>(), ctx->scan_tmp, &found));
     if (found < 0 || found > n) return fail(ctx, NWG_ERR_HIP, "nwg_sample_surface: the output slots do not add up");
     if (found == 0) return NWG_OK;
     if (found > max_points) return fail(ctx, NWG_ERR_CAPACITY, "nwg_sample_surface: " + std::to_string(found) + " detected nodes, max_points is " + std::to_string(max_points));
@@ -663,13 +642,11 @@ NWG_EXPORT int nwg_displace(nwg_ctx *ctx, const double *xyz, const double *sigma
 {
     if (!xyz || !sigma || !out || !count_ok(n)) return NWG_ERR_BADARG;
     if (!ctx) return NWG_ERR_BADARG;
-    if (!finite_array(xyz, 3 * n) || !finite_array(sigma, 3 * n)) return fail(ctx, NWG_ERR_NONFINITE, "nwg_displace: a coordinate or a sigma is not finite");
+    if (!bq::all_finite(xyz, 3 * n) || !bq::all_finite(sigma, 3 * n)) return fail(ctx, NWG_ERR_NONFINITE, "nwg_displace: a coordinate or a sigma is not finite");
     NWG_HIP(hipSetDevice(ctx->device));
     const size_t bytes = sizeof(double) * 3 * (size_t)n;
-    int r = upload(ctx, ctx->in0, xyz, bytes);
-    if (r != NWG_OK) return r;
-    r = upload(ctx, ctx->in1, sigma, bytes);
-    if (r != NWG_OK) return r;
+    NWG_HIP(bq::upload(ctx->stream, ctx->in0, xyz, 3 * n));
+    NWG_HIP(bq::upload(ctx->stream, ctx->in1, sigma, 3 * n));
     NWG_HIP(ctx->out0.ensure(bytes));
     hipLaunchKernelGGL(k_sim_displace, dim3(nblk(n)), dim3(NWG_BLOCK), 0, ctx->stream, ctx->in0.as<double>(), ctx->in1.as<double>(), (int)n, (u64)seed, stream,
                        ctx->out0.as<double>());
@@ -686,45 +663,32 @@ NWG_EXPORT int nwg_smlmify(nwg_ctx *ctx, const double *xyz, const double *sigma,
     if (!xyz || !sigma || !xyz_out || !sigma_out || n < 1 || n > (1ll << 30) / NWG_COPIES || sz < 1 || sz > NWG_COPIES * n) return NWG_ERR_BADARG;
     if (!model_ok(model, psf_width, mean_photon_count, bg_photon_count)) return NWG_ERR_BADARG;
     if (!ctx) return NWG_ERR_BADARG;
-    if (!finite_array(xyz, 3 * n) || !finite_array(sigma, 3 * n)) return fail(ctx, NWG_ERR_NONFINITE, "nwg_smlmify: a coordinate or a sigma is not finite");
+    if (!bq::all_finite(xyz, 3 * n) || !bq::all_finite(sigma, 3 * n)) return fail(ctx, NWG_ERR_NONFINITE, "nwg_smlmify: a coordinate or a sigma is not finite");
     NWG_HIP(hipSetDevice(ctx->device));
     const int nc = (int)(NWG_COPIES * n);
-    int r = upload(ctx, ctx->in0, xyz, sizeof(double) * 3 * (size_t)n);
-    if (r != NWG_OK) return r;
-    r = upload(ctx, ctx->in1, sigma, sizeof(double) * 3 * (size_t)n);
-    if (r != NWG_OK) return r;
-    // the sz-th smallest key, a byte per pass from the top: `rank` is its 0-based rank among the keys that agree with `prefix`
+    NWG_HIP(bq::upload(ctx->stream, ctx->in0, xyz, 3 * n));
+    NWG_HIP(bq::upload(ctx->stream, ctx->in1, sigma, 3 * n));
+    // the sz-th smallest key; `rank` is what is left of its 0-based rank among the copies that hold the same key
     NWG_HIP(ctx->hist.ensure(sizeof(u32) * 256));
-    u64 prefix = 0;
-    int64_t rank = sz - 1;
-    const int hist_blocks = std::min(nblk(nc), 2048);
-    for (int shift = 56; shift >= 0; shift -= 8) {
-        u32 hist[256];
-        NWG_HIP(hipMemsetAsync(ctx->hist.p, 0, sizeof(hist), ctx->stream));
-        hipLaunchKernelGGL(k_sim_copy_hist, dim3(hist_blocks), dim3(NWG_BLOCK), 0, ctx->stream, nc, (u64)seed, stream_key, prefix, shift, ctx->hist.as<u32>());
-        NWG_HIP(hipGetLastError());
-        NWG_HIP(hipMemcpyAsync(hist, ctx->hist.p, sizeof(hist), hipMemcpyDeviceToHost, ctx->stream));
-        NWG_HIP(hipStreamSynchronize(ctx->stream));
-        int b = 0;
-        while (b < 256 && rank >= (int64_t)hist[b]) rank -= hist[b++];
-        if (b == 256) return fail(ctx, NWG_ERR_HIP, "nwg_smlmify: the key histogram does not reach the rank");
-        prefix = (prefix << 8) | (u64)b;
-    }
-    const u64 threshold = prefix;
+    uint64_t threshold = 0;
+    int64_t rank = -1;
+    const auto pass = [&](uint64_t prefix, int shift, unsigned *hist) {
+        hipLaunchKernelGGL(k_sim_copy_hist, dim3(std::min(nblk(nc), 2048)), dim3(NWG_BLOCK), 0, ctx->stream, nc, (u64)seed, stream_key, (u64)prefix, shift, hist);
+    };
+    NWG_HIP(bq::select_u64(ctx->stream, ctx->hist.as<u32>(), 56, pass, [&](int64_t) { return sz - 1; }, &threshold, &rank));
+    if (rank < 0) return fail(ctx, NWG_ERR_HIP, "nwg_smlmify: the key histogram does not reach the rank");
     const int n_equal = (int)rank + 1;                        // of the copies whose key equals the threshold, the first n_equal are kept
     NWG_HIP(ctx->flag.ensure(sizeof(int) * (size_t)nc));
     NWG_HIP(ctx->slot.ensure(sizeof(int) * ((size_t)nc + 1)));
     NWG_HIP(ctx->cells0.ensure(sizeof(int) * ((size_t)nc + 1)));                   // (the rank among equal keys; free between two lattices)
-    hipLaunchKernelGGL(k_sim_copy_equal, dim3(nblk(nc)), dim3(NWG_BLOCK), 0, ctx->stream, nc, (u64)seed, stream_key, threshold, ctx->flag.as<int>());
+    hipLaunchKernelGGL(k_sim_copy_equal, dim3(nblk(nc)), dim3(NWG_BLOCK), 0, ctx->stream, nc, (u64)seed, stream_key, (u64)threshold, ctx->flag.as<int>());
     NWG_HIP(hipGetLastError());
     NWG_HIP(bq::scan_exclusive(ctx->stream, ctx->flag.as<int>(), nc, ctx->cells0.as<int>(), ctx->scan_tmp));
-    hipLaunchKernelGGL(k_sim_copy_keep, dim3(nblk(nc)), dim3(NWG_BLOCK), 0, ctx->stream, nc, (u64)seed, stream_key, threshold, ctx->cells0.as<int>(), n_equal,
+    hipLaunchKernelGGL(k_sim_copy_keep, dim3(nblk(nc)), dim3(NWG_BLOCK), 0, ctx->stream, nc, (u64)seed, stream_key, (u64)threshold, ctx->cells0.as<int>(), n_equal,
                        ctx->flag.as<int>());
     NWG_HIP(hipGetLastError());
-    NWG_HIP(bq::scan_exclusive(ctx->stream, ctx->flag.as<int>(), nc, ctx->slot.as<int>(), ctx->scan_tmp));
     int total = -1;
-    NWG_HIP(hipMemcpyAsync(&total, ctx->slot.as<int>() + nc, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    NWG_HIP(hipStreamSynchronize(ctx->stream));
+    NWG_HIP(bq::scan_total(ctx->stream, ctx->flag.as<int>(), nc, ctx->slot.as<int>(), ctx->scan_tmp, &total));
     if (total != sz) return fail(ctx, NWG_ERR_HIP, "nwg_smlmify: the selection kept " + std::to_string(total) + " copies, not " + std::to_string(sz));
     const size_t bytes = sizeof(double) * 3 * (size_t)sz;
     NWG_HIP(ctx->out0.ensure(bytes));
@@ -743,7 +707,7 @@ NWG_EXPORT int nwg_smlmify(nwg_ctx *ctx, const double *xyz, const double *sigma,
 
 NWG_EXPORT int nwg_background(nwg_ctx *ctx, const double *lo, const double *hi, int64_t n, uint64_t seed, uint32_t stream, double *xyz_out)
 {
-    if (!lo || !hi || !xyz_out || !count_ok(n) || !finite_array(lo, 3) || !finite_array(hi, 3)) return NWG_ERR_BADARG;
+    if (!lo || !hi || !xyz_out || !count_ok(n) || !bq::all_finite(lo, 3) || !bq::all_finite(hi, 3)) return NWG_ERR_BADARG;
     if (!ctx) return NWG_ERR_BADARG;
     NWG_HIP(hipSetDevice(ctx->device));
     sim_box b;

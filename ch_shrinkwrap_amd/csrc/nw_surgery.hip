@@ -5,7 +5,7 @@
 //   k_ws_init / k_ws_hook / k_ws_compress   union-find over the twin table (ECL-CC): a face hooks the larger of two roots onto the smaller
 //                                           with atomicCAS, so every root is its component's minimum face id whatever the schedule; one
 //                                           hooking launch, however long the component (no propagation rounds);
-//   bq::scan_exclusive + k_ws_number        roots are flagged, scanned (the block-boundary units' shared scan, nw_bq.h) and every face
+//   bq::scan_total + k_ws_number            roots are flagged, scanned (the query units' shared scan, nw_bq.h) and every face
 //                                           takes its root's rank: labels in order of the components' smallest face ids;
 //   k_ws_stats                              one thread per face, float64 terms turned into 64-bit fixed point and summed by wave when the
 //                                           wave's faces share a label (the usual case), by lane otherwise: integer sums, the same bytes
@@ -407,13 +407,6 @@ int check_label(const int32_t *label, int64_t nf, int32_t nc)
     return NWS_OK;
 }
 
-template <class T> int upload(nws_ctx *ctx, DevBuf &buf, const T *src, int64_t n)
-{
-    NWS_HIP(buf.ensure(sizeof(T) * (size_t)n));
-    NWS_HIP(hipMemcpyAsync(buf.p, src, sizeof(T) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    return NWS_OK;
-}
-
 // 2^k with n_terms * bound * 2^k <= 2^62: the fixed-point scale of a sum of n_terms terms of magnitude <= bound
 double fixed_scale(double n_terms, double bound)
 {
@@ -475,10 +468,10 @@ NWS_EXPORT int nws_label_faces(nws_ctx *ctx, const int32_t *faces, const int32_t
     if (!ctx) return NWS_ERR_BADARG;
     NWS_HIP(hipSetDevice(ctx->device));
     const int nf = (int)n_faces;
-    NWS_TRY(upload(ctx, ctx->twin, twin, 3 * n_faces));
+    NWS_HIP(bq::upload(ctx->stream, ctx->twin, twin, 3 * n_faces));
     const unsigned char *dmask = nullptr;
     if (mask) {
-        NWS_TRY(upload(ctx, ctx->a, mask, n_faces));
+        NWS_HIP(bq::upload(ctx->stream, ctx->a, mask, n_faces));
         dmask = ctx->a.as<unsigned char>();
     }
     NWS_HIP(ctx->b.ensure(sizeof(int) * (size_t)nf));            // parent
@@ -490,11 +483,10 @@ NWS_EXPORT int nws_label_faces(nws_ctx *ctx, const int32_t *faces, const int32_t
     hipLaunchKernelGGL(k_ws_hook, dim3(nblk(nf)), dim3(NWS_BLOCK), 0, ctx->stream, ctx->twin.as<int>(), nf, parent);
     hipLaunchKernelGGL(k_ws_compress, dim3(nblk(nf)), dim3(NWS_BLOCK), 0, ctx->stream, nf, parent, label, is_root);
     NWS_HIP(hipGetLastError());
-    NWS_HIP(bq::scan_exclusive(ctx->stream, is_root, nf, rank, ctx->e));
+    int nc = 0;
+    NWS_HIP(bq::scan_total(ctx->stream, is_root, nf, rank, ctx->e, &nc));
     hipLaunchKernelGGL(k_ws_number, dim3(nblk(nf)), dim3(NWS_BLOCK), 0, ctx->stream, nf, rank, label);
     NWS_HIP(hipGetLastError());
-    int nc = 0;
-    NWS_HIP(hipMemcpyAsync(&nc, rank + nf, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     NWS_HIP(hipMemcpyAsync(label_out, label, sizeof(int) * (size_t)nf, hipMemcpyDeviceToHost, ctx->stream));
     NWS_HIP(hipStreamSynchronize(ctx->stream));
     *n_components_out = nc;
@@ -513,10 +505,10 @@ NWS_EXPORT int nws_component_stats(nws_ctx *ctx, const float *pos, int64_t n_ver
     if (n_components == 0) return NWS_OK;
     NWS_HIP(hipSetDevice(ctx->device));
     const int nf = (int)n_faces, nc = n_components;
-    NWS_TRY(upload(ctx, ctx->pos, pos, 3 * n_vertices));
-    NWS_TRY(upload(ctx, ctx->faces, faces, 3 * n_faces));
-    NWS_TRY(upload(ctx, ctx->twin, twin, 3 * n_faces));
-    NWS_TRY(upload(ctx, ctx->label, label, n_faces));
+    NWS_HIP(bq::upload(ctx->stream, ctx->pos, pos, 3 * n_vertices));
+    NWS_HIP(bq::upload(ctx->stream, ctx->faces, faces, 3 * n_faces));
+    NWS_HIP(bq::upload(ctx->stream, ctx->twin, twin, 3 * n_faces));
+    NWS_HIP(bq::upload(ctx->stream, ctx->label, label, n_faces));
     const ws_frame fr = make_frame(pos, n_vertices, nf);
     NWS_TRY(run_stats(ctx, nf, nc, fr));
     std::vector<u64> acc(7 * (size_t)nc);
@@ -551,8 +543,7 @@ NWS_EXPORT int nws_winding(nws_ctx *ctx, const float *pos, int64_t n_vertices, c
         return NWS_ERR_BADARG;
     if (!bq::mesh_ok(pos, n_vertices, faces, n_faces)) return NWS_ERR_BADARG;
     NWS_TRY(check_label(label, n_faces, n_components));
-    for (int64_t i = 0; i < 3 * n_queries; ++i)
-        if (!std::isfinite(queries[i])) return NWS_ERR_BADARG;
+    if (!bq::all_finite(queries, 3 * n_queries)) return NWS_ERR_BADARG;
     if (query_component)
         for (int64_t i = 0; i < n_queries; ++i)
             if (query_component[i] < -1 || query_component[i] >= n_components) return NWS_ERR_BADARG;
@@ -561,13 +552,13 @@ NWS_EXPORT int nws_winding(nws_ctx *ctx, const float *pos, int64_t n_vertices, c
     if (nw == 0) return NWS_OK;
     NWS_HIP(hipSetDevice(ctx->device));
     const int nf = (int)n_faces, nc = n_components, nq = (int)n_queries;
-    NWS_TRY(upload(ctx, ctx->pos, pos, 3 * n_vertices));
-    NWS_TRY(upload(ctx, ctx->faces, faces, 3 * n_faces));
-    NWS_TRY(upload(ctx, ctx->label, label, n_faces));
-    NWS_TRY(upload(ctx, ctx->a, queries, 3 * n_queries));
+    NWS_HIP(bq::upload(ctx->stream, ctx->pos, pos, 3 * n_vertices));
+    NWS_HIP(bq::upload(ctx->stream, ctx->faces, faces, 3 * n_faces));
+    NWS_HIP(bq::upload(ctx->stream, ctx->label, label, n_faces));
+    NWS_HIP(bq::upload(ctx->stream, ctx->a, queries, 3 * n_queries));
     const int *dqc = nullptr;
     if (query_component) {
-        NWS_TRY(upload(ctx, ctx->b, query_component, n_queries));
+        NWS_HIP(bq::upload(ctx->stream, ctx->b, query_component, n_queries));
         dqc = ctx->b.as<int>();
     }
     // the boxes: k_ws_stats over a twin table of -1 (the border counts it also makes are not read)
@@ -599,8 +590,8 @@ NWS_EXPORT int nws_short_edge_vertices(nws_ctx *ctx, const float *pos, int64_t n
     if (!ctx) return NWS_ERR_BADARG;
     NWS_HIP(hipSetDevice(ctx->device));
     const int nh = (int)(3 * n_faces);
-    NWS_TRY(upload(ctx, ctx->pos, pos, 3 * n_vertices));
-    NWS_TRY(upload(ctx, ctx->faces, faces, 3 * n_faces));
+    NWS_HIP(bq::upload(ctx->stream, ctx->pos, pos, 3 * n_vertices));
+    NWS_HIP(bq::upload(ctx->stream, ctx->faces, faces, 3 * n_faces));
     NWS_HIP(ctx->a.ensure(sizeof(float) * (size_t)nh));          // lengths
     NWS_HIP(ctx->b.ensure(sizeof(int) * 512));                   // two histograms
     NWS_HIP(ctx->c.ensure(sizeof(ws_sel)));

@@ -1,5 +1,6 @@
 """CPU test: libnanowrap_hip.so exports every function include/nw_evaluation.h declares, the binding names the same set, the kernels of
-csrc/nw_evaluation.hip stay within their budgets, and the calls check their arguments before they touch a GPU."""
+csrc/nw_evaluation.hip and of the point grid it shares with hole punching (csrc/nw_bq.hip) stay within their budgets, and the calls check
+their arguments before they touch a GPU."""
 import ctypes
 import os
 import re
@@ -7,7 +8,11 @@ import re
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = ['k_ev_face_setup', 'k_ev_node_test', 'k_ev_emit', 'k_ev_bbox', 'k_ev_cell_count', 'k_ev_scatter', 'k_ev_nearest', 'k_ev_sum_final']
+KERNELS = ['k_ev_face_setup', 'k_ev_node_test', 'k_ev_emit', 'k_ev_nearest', 'k_ev_sum_final']
+# the grid's kernels, once this unit's and hole punching's own (k_ev_* / k_hp_bbox, _cell_count, _scatter), with the budgets they had there
+GRID_KERNELS = {'k_bq_bbox_f64': (48, 0), 'k_bq_cell_count_f64': (48, 0), 'k_bq_scatter_f64': (16, 0),
+                'k_bq_bbox_f32': (32, 0), 'k_bq_cell_count_f32': (32, 0), 'k_bq_scatter_f32': (32, 0)}
+SCAN_KERNELS = ['k_bq_scan_tiles', 'k_bq_scan_bsums', 'k_bq_scan_final']
 
 
 def _declared():
@@ -31,11 +36,15 @@ def test_library_exports_the_evaluation_header():
 def test_evaluation_kernels_are_budgeted_and_within_budget():
     from ch_shrinkwrap_amd import build
     build.build_hip_library()
-    assert build.OBJ_EVALUATION in build.BUDGETED_OBJECTS
+    assert build.OBJ_EVALUATION in build.BUDGETED_OBJECTS and build.OBJ_BQ in build.BUDGETED_OBJECTS
     in_object = build.kernel_resources(build.OBJ_EVALUATION)
     assert sorted(in_object) == sorted(KERNELS)                  # every kernel of the unit has a row, and no row is stale
+    assert sorted(build.kernel_resources(build.OBJ_BQ)) == sorted(list(GRID_KERNELS) + SCAN_KERNELS)
+    assert not [k for k in build.KERNEL_BUDGETS if k.startswith('k_ev_') and k not in KERNELS]
+    for k, budget in GRID_KERNELS.items():
+        assert build.KERNEL_BUDGETS[k] == budget, k
     res = build.check_kernel_budgets()
-    for k in KERNELS:
+    for k in KERNELS + list(GRID_KERNELS):
         assert k in build.KERNEL_BUDGETS
         r = res[k]
         assert r['scratch'] == 0 and r['vgpr_spill'] == 0 and r['sgpr_spill'] == 0, (k, r)
