@@ -39,7 +39,7 @@ OBJ_SIMULATION = _csrc('nw_simulation.o')
 # the translation units of libnanowrap_hip.so: (source, object, what else it is rebuilt for, flags).  The objects are linked in this order.
 UNITS = [
     # the per-iteration kernels and the C-ABI; every header of csrc/ but nw_bq.h and nw_bq_core.h is included by it (directly or through
-    # nw_kernels.h)
+    # nw_kernels.h), nw_host_copy.h among them: the HIP-free host half of the result hand-back, which the tests also compile for the CPU
     (_csrc('nanowrap.hip'), OBJ_MAIN, sorted(set(glob.glob(_csrc('*.h'))) - set(_BQ_H)) + [_include('nanowrap.h')],
      [f for f in HIPCC_FLAGS if f != '-shared']),
     # set-up radix sort (hipCUB)

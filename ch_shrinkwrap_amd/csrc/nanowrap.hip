@@ -12,14 +12,11 @@
 #include <algorithm>
 #include <chrono>
 #include <thread>
-#include <mutex>
-#include <condition_variable>
-#include <functional>
 #include <atomic>
-#include <memory>
 
 #include "../../include/nanowrap.h"
 #include "nw_kernels.h"
+#include "nw_host_copy.h"       // the copy threads (NwHostPool), the row copier and the chunked copy-out: plain host C++, tested on the CPU
 
 // stable LSD radix sort of (key, value) pairs on the device (csrc/nw_sort.hip, hipCUB); returns a hipError_t as int
 int nw_sort_pairs_u32(const unsigned *key_in, unsigned *key_out, const int *val_in, int *val_out, int n, int bits, hipStream_t stream);
@@ -92,137 +89,6 @@ struct DevBuf {
 enum { ST_TOTAL = 0, ST_GRID = 1, ST_NN = 2, ST_ATTRACT = 3, ST_PRIOR = 4, ST_AS = 5, ST_UPDATE = 6, ST_FIXUP = 7, ST_COUNT = 8 };
 
 }  // namespace
-
-// Small persistent host thread pool for the write-back (the strided copy into the caller's vertex records is host-memory bound: one
-// thread moves ~0.4 GB/s of 12-byte rows).  A job is a number of CHUNKS taken from a shared counter by whoever is awake -- the calling
-// thread included -- and it ends when every chunk has been done, not when every thread has shown up: a thread the scheduler wakes late
-// (the GPU boxes' hosts are shared; a woken thread can arrive 15 ms later) finds the counter exhausted and goes back to sleep, instead
-// of holding the block up (round 5).  arm(): work is about to come -- the threads wake now and spin for it for a bounded time.
-struct NwHostPool {
-    struct Job { std::function<void(int)> fn; int n = 0; std::atomic<int> next{0}, done{0}; };
-    std::vector<std::thread> th;
-    std::mutex m;
-    std::condition_variable cv_work;
-    std::shared_ptr<Job> job;
-    std::atomic<unsigned long> generation{0};
-    unsigned long arm_generation = 0;
-    bool stop = false;
-    int n = 1;
-    static void work(Job &j)
-    {
-        for (;;) {
-            const int c = j.next.fetch_add(1, std::memory_order_relaxed);
-            if (c >= j.n) break;
-            j.fn(c);
-            j.done.fetch_add(1, std::memory_order_release);
-        }
-    }
-    void start(int threads, int device)
-    {
-        n = threads < 1 ? 1 : threads;
-        for (int t = 1; t < n; ++t)
-            th.emplace_back([this, device] {
-                (void)hipSetDevice(device);
-                unsigned long seen = 0, seen_arm = 0;
-                for (;;) {
-                    std::shared_ptr<Job> j;
-                    {
-                        std::unique_lock<std::mutex> lk(m);
-                        cv_work.wait(lk, [&] { return stop || generation.load() != seen || arm_generation != seen_arm; });
-                        if (stop) return;
-                        if (generation.load() == seen) {
-                            // armed: spin for the job (bounded), then take it like a woken thread
-                            seen_arm = arm_generation;
-                            lk.unlock();
-                            const auto t0 = std::chrono::steady_clock::now();
-                            while (generation.load(std::memory_order_acquire) == seen) {
-                                for (int k = 0; k < 32; ++k) __builtin_ia32_pause();
-                                if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(1500)) break;
-                            }
-                            lk.lock();
-                            if (stop) return;
-                            if (generation.load() == seen) continue;          // nothing came: back to sleep
-                        }
-                        seen_arm = arm_generation;
-                        seen = generation.load();
-                        j = job;
-                    }
-                    if (j) work(*j);
-                }
-            });
-    }
-    void arm()
-    {
-        if (n <= 1) return;
-        {
-            std::lock_guard<std::mutex> lk(m);
-            ++arm_generation;
-        }
-        cv_work.notify_all();
-    }
-    // a job in the BACKGROUND: the pool's threads work through it while the caller goes on (a block's strided mesh records, written
-    // while the next block runs on the GPU); wait_posted() lends a hand with what is left and returns when it is done
-    std::shared_ptr<Job> posted;
-    void post_chunks(int nchunks, const std::function<void(int)> &f)
-    {
-        wait_posted();
-        if (nchunks <= 0) return;
-        if (n <= 1) { for (int c = 0; c < nchunks; ++c) f(c); return; }
-        auto j = std::make_shared<Job>();
-        j->fn = f; j->n = nchunks;
-        {
-            std::lock_guard<std::mutex> lk(m);
-            job = j;
-            generation.fetch_add(1, std::memory_order_release);
-        }
-        cv_work.notify_all();
-        posted = j;
-    }
-    void wait_posted()
-    {
-        if (!posted) return;
-        std::shared_ptr<Job> j = posted;
-        posted.reset();
-        work(*j);
-        while (j->done.load(std::memory_order_acquire) < j->n)
-            for (int k = 0; k < 8; ++k) __builtin_ia32_pause();
-        std::lock_guard<std::mutex> lk(m);
-        if (job == j) job.reset();
-    }
-    // f(c) for c in [0, nchunks), each exactly once, on whichever threads are awake; returns when all have been done
-    void run_chunks(int nchunks, const std::function<void(int)> &f)
-    {
-        wait_posted();
-        if (nchunks <= 0) return;
-        if (n <= 1 || nchunks == 1) { for (int c = 0; c < nchunks; ++c) f(c); return; }
-        auto j = std::make_shared<Job>();
-        j->fn = f; j->n = nchunks;
-        {
-            std::lock_guard<std::mutex> lk(m);
-            job = j;
-            generation.fetch_add(1, std::memory_order_release);
-        }
-        cv_work.notify_all();
-        work(*j);
-        while (j->done.load(std::memory_order_acquire) < nchunks)
-            for (int k = 0; k < 8; ++k) __builtin_ia32_pause();
-        {
-            std::lock_guard<std::mutex> lk(m);
-            if (job == j) job.reset();
-        }
-    }
-    void run(const std::function<void(int)> &f) { run_chunks(n, f); }
-    void shutdown()
-    {
-        {
-            std::lock_guard<std::mutex> lk(m);
-            stop = true;
-        }
-        cv_work.notify_all();
-        for (auto &t : th) t.join();
-        th.clear();
-    }
-};
 
 struct nw_ctx {
     int device = 0;
@@ -412,6 +278,10 @@ int fail(nw_ctx *c, int code, const std::string &msg)
     if (c) c->err = msg;
     return code;
 }
+
+// the two shapes most of the environment knobs have: on unless set to 0, and the level of NW_VERBOSE (0 when unset)
+bool env_on(const char *name) { const char *e = getenv(name); return !(e && atoi(e) == 0); }
+int verbose_level() { const char *e = getenv("NW_VERBOSE"); return e ? atoi(e) : 0; }
 
 #define NW_HIP(call)                                                                                         \
     do {                                                                                                     \
@@ -934,7 +804,7 @@ NW_EXPORT int nw_set_points(nw_ctx *ctx, const float *xyz, int64_t n_points, con
     ctx->item_level = -1;
     ctx->nitems = 0;
     ctx->face_warm = false;
-    if (getenv("NW_VERBOSE") && atoi(getenv("NW_VERBOSE")) >= 2) fprintf(stderr, "[nanowrap] warm start dropped (%s)\n", __func__);
+    if (verbose_level() >= 2) fprintf(stderr, "[nanowrap] warm start dropped (%s)\n", __func__);
     ctx->proj_ready = false; ctx->proj_sorted = false;
     ctx->tuned = false; ctx->cell_tune = 1.0; ctx->blocks_done = 0;
     ctx->last_mean_dist = -1.0;
@@ -979,7 +849,7 @@ NW_EXPORT int nw_set_data(nw_ctx *ctx, const float *data)
 // name a vertex outside the mesh keep their place in line (the ring-table pass has reported them, or the first query will).
 static int sort_faces(nw_ctx *ctx)
 {
-    static const bool on = !(getenv("NW_FACE_ORDER") && atoi(getenv("NW_FACE_ORDER")) == 0);
+    static const bool on = env_on("NW_FACE_ORDER");
     ctx->face_sorted = false;
     if (!on || ctx->F < 2) return NW_OK;
     const int64_t F = ctx->F, M = ctx->M;
@@ -1072,7 +942,7 @@ NW_EXPORT int nw_set_mesh(nw_ctx *ctx, const float *pos, const float *nrm, const
     else NW_TRY(nw_refresh_normals(ctx, nullptr, 0.0));         // area-weighted vertex normals from positions + faces on the device
     if (topo_change) { ctx->grid_valid = false; }
     ctx->face_warm = false;                               // face ids of another topology are no starting guess
-    if (getenv("NW_VERBOSE") && atoi(getenv("NW_VERBOSE")) >= 2) fprintf(stderr, "[nanowrap] warm start dropped (%s)\n", __func__);
+    if (verbose_level() >= 2) fprintf(stderr, "[nanowrap] warm start dropped (%s)\n", __func__);
     ctx->have_owned = false;
     ctx->have_boundary = false; ctx->have_peers = false; ctx->pos_unpack_pending = false;      // (a sharding belongs to the mesh it was made for)
     // a new mesh object = a new optimiser in the reference (_membrane_mesh.pyx:1510): history restarts
@@ -1406,9 +1276,9 @@ static nw_ctx::BlockGraph *block_graph(nw_ctx *ctx, int num_iters, bool head = f
 static int tune_grid(nw_ctx *ctx)
 {
     if (ctx->tuned) return NW_OK;
-    const char *at = getenv("NW_AUTOTUNE");
-    if ((at && atoi(at) == 0) || getenv("NW_CELL_SIZE") || getenv("NW_CELL_FACTOR") || ctx->N < 20000 || !ctx->face_warm) {
-        if (ctx->face_warm || (at && atoi(at) == 0)) ctx->tuned = true;
+    const bool autotune = env_on("NW_AUTOTUNE");
+    if (!autotune || getenv("NW_CELL_SIZE") || getenv("NW_CELL_FACTOR") || ctx->N < 20000 || !ctx->face_warm) {
+        if (ctx->face_warm || !autotune) ctx->tuned = true;
         return NW_OK;
     }
     ctx->tuned = true;
@@ -1459,7 +1329,7 @@ static int tune_grid(nw_ctx *ctx)
 // slowest waves, and a cloud of a few hundred thousand localizations is a single round of waves -- the heavy ones must not start last.
 static int order_items_by_cost(nw_ctx *ctx)
 {
-    static const bool on = !(getenv("NW_ITEM_ORDER") && atoi(getenv("NW_ITEM_ORDER")) == 0);
+    static const bool on = env_on("NW_ITEM_ORDER");
     if (!on || ctx->items_by_cost || !ctx->item_cost_valid || ctx->nitems < 2) return NW_OK;
     const int n = ctx->nitems;
     // a few thousand items: done on the host
@@ -1473,7 +1343,7 @@ static int order_items_by_cost(nw_ctx *ctx)
     const double median = std::max(1.0, (double)tmp[n / 2]);
     // While the list is shorter than two rounds of waves the launch ends on its heaviest items: those are cut into pieces of about the
     // median cost (a piece repeats the item's walk over fewer localizations -- more work in all, shorter waves).
-    static const bool split_on = !(getenv("NW_ITEM_SPLIT") && atoi(getenv("NW_ITEM_SPLIT")) == 0);
+    static const bool split_on = env_on("NW_ITEM_SPLIT");
     const bool split = split_on && n < 2 * 256 * 4 * 6;
     struct Piece { NwItem it; double est; };
     std::vector<Piece> out;
@@ -1583,7 +1453,7 @@ NW_EXPORT int nw_search_begin(nw_ctx *ctx, const float *lams, int n_lams, int nu
     ctx->search_flags = flags & ~(NW_FLAG_RESULT_TO_HOST | NW_FLAG_COMM_TILES | NW_FLAG_COMM_REPLICATED | NW_FLAG_COMM_HALO | NW_FLAG_ROWS_ASYNC);
     ctx->rows_async = (flags & NW_FLAG_ROWS_ASYNC) != 0 && ctx->wb_rows != nullptr;
     ctx->direct_out = false;
-    if ((flags & NW_FLAG_RESULT_TO_HOST) && num_iters > 0 && 3 * ctx->M * sizeof(float) <= (4u << 20) && !(getenv("NW_DIRECT_OUT") && atoi(getenv("NW_DIRECT_OUT")) == 0)) {
+    if ((flags & NW_FLAG_RESULT_TO_HOST) && num_iters > 0 && 3 * ctx->M * sizeof(float) <= (4u << 20) && env_on("NW_DIRECT_OUT")) {
         NW_TRY(ensure_staging(ctx));                // (larger results: the sliced copy of nw_search_end is the faster one)
         ctx->direct_out = true;
     }
@@ -1632,11 +1502,11 @@ static int enqueue_begin_ops(nw_ctx *ctx)
 // (`parts`: 1 grid build, 2 the query kernel, 4 fix-up -- a block captured for sampled profiling launches part 2 of its first
 // iteration outside the graphs, between two events)
 // the query kernel resolves its ambiguous localizations itself (default); NW_FUSE_FIXUP=0 brings back the separate fix-up launch
-static bool fuse_fixup() { static const bool on = !(getenv("NW_FUSE_FIXUP") && atoi(getenv("NW_FUSE_FIXUP")) == 0); return on; }
+static bool fuse_fixup() { static const bool on = env_on("NW_FUSE_FIXUP"); return on; }
 
 // the ring half of the curvature prior rides in the query launch (workgroups appended to its grid: they run in its drain); NW_RING_IN_NN=0
 // (developer knob) makes it a launch of its own in front of k_prior_directions
-static bool ring_in_nn() { static const bool on = !(getenv("NW_RING_IN_NN") && atoi(getenv("NW_RING_IN_NN")) == 0); return on; }
+static bool ring_in_nn() { static const bool on = env_on("NW_RING_IN_NN"); return on; }
 static NwRingArgs ring_args(const nw_ctx *ctx)
 {
     NwRingArgs r;
@@ -1646,7 +1516,7 @@ static NwRingArgs ring_args(const nw_ctx *ctx)
 
 // the attraction step rides in the query launch too (one workgroup per workgroup of the query, appended behind the ring workgroups: they fill
 // the launch's drain); NW_ATTRACT_IN_NN=0 (developer knob): k_attract as a launch of its own behind the query
-static bool attract_in_nn() { static const bool on = !(getenv("NW_ATTRACT_IN_NN") && atoi(getenv("NW_ATTRACT_IN_NN")) == 0); return on; }
+static bool attract_in_nn() { static const bool on = env_on("NW_ATTRACT_IN_NN"); return on; }
 static int launch_query(nw_ctx *ctx, int it, int parts, bool with_ring, bool with_attract, bool *attract_rode)
 {
     if (attract_rode) *attract_rode = false;
@@ -1654,7 +1524,7 @@ static int launch_query(nw_ctx *ctx, int it, int parts, bool with_ring, bool wit
     const NwGrid g = ctx->grid;
     if (parts & QP_GRID) {
         StageScope s(ctx, ST_GRID);
-        static const bool tile_fuse = !(getenv("NW_TILE_FUSE") && atoi(getenv("NW_TILE_FUSE")) == 0);      // developer knob: 0 = the scan's own first pass
+        static const bool tile_fuse = env_on("NW_TILE_FUSE");      // developer knob: 0 = the scan's own first pass
         int *tiles = tile_fuse ? ctx->ctile.p : nullptr;
         hipLaunchKernelGGL(k_face_centroids, dim3(nblk(F)), dim3(NW_BLOCK), 0, ctx->stream, g, ctx->pos.p, ctx->faces.p, (int)F,
                            ctx->cent_tmp.p, ctx->fcell.p, ctx->frank.p, ctx->ccount.p, tiles, ctx->ambig_count.p, ctx->state.p, it, ctx->query_serial.p);
@@ -1799,7 +1669,7 @@ static int ensure_pin_log(nw_ctx *ctx, int n_records)
 
 // The end of a block as a word in pinned memory (k_block_done): queued behind the block's last kernel by nw_search when the result is
 // staged by that kernel.  NW_SPIN_WAIT=0 (developer knob): the blocking hipStreamSynchronize of round 4.
-static bool spin_wait_on() { static const bool on = !(getenv("NW_SPIN_WAIT") && atoi(getenv("NW_SPIN_WAIT")) == 0); return on; }
+static bool spin_wait_on() { static const bool on = env_on("NW_SPIN_WAIT"); return on; }
 static int enqueue_block_done(nw_ctx *ctx)
 {
     ctx->done_launched = false;
@@ -1852,19 +1722,19 @@ static int enqueue_sliced_result(nw_ctx *ctx)
 static bool wait_block_done(nw_ctx *ctx, int want)
 {
     if (!ctx->done_launched) return false;
-    volatile int *flag = ctx->pin_flag;
+    const int *flag = ctx->pin_flag;
     const auto t0 = ctx->block_t0;
     const double expect_us = ctx->block_us_ema;
     bool armed = false;
     long spins = 0;
     for (;;) {
-        if (*flag - want >= 0) break;
+        if (nw_flag_load(flag) - want >= 0) break;
         for (int k = 0; k < 8; ++k) __builtin_ia32_pause();
         if ((++spins & 63) == 0) {
             const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
             if (!armed && ctx->pool && expect_us > 0 && us > expect_us - 250.0) { ctx->pool->arm(); armed = true; }
             if (us > 2000.0 + 20.0 * expect_us) {                      // far beyond anything a healthy block takes: let the runtime say what happened
-                if (hipStreamQuery(ctx->stream) != hipErrorNotReady) { (void)hipGetLastError(); return *flag - want >= 0; }
+                if (hipStreamQuery(ctx->stream) != hipErrorNotReady) { (void)hipGetLastError(); return nw_flag_load(flag) - want >= 0; }
                 if (us > 30e6) return false;
             }
         }
@@ -1913,12 +1783,12 @@ NW_EXPORT int nw_search_end(nw_ctx *ctx, float *pos_out, nw_iter_log *log, int *
             const auto tcp0 = std::chrono::steady_clock::now();
             if (last_ran) {
                 copy_out_staged(ctx, pos_out, ctx->wb_rows, ctx->wb_stride);
-                if (getenv("NW_VERBOSE") && atoi(getenv("NW_VERBOSE")) >= 3)
+                if (verbose_level() >= 3)
                     fprintf(stderr, "[nanowrap] search_end: copy-out of the staged result alone %ld us\n", (long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - tcp0).count());
             } else {
                 NW_TRY(write_back_impl(ctx, pos_out, ctx->wb_rows, ctx->wb_stride));
             }
-            if (getenv("NW_VERBOSE") && atoi(getenv("NW_VERBOSE")) >= 3)
+            if (verbose_level() >= 3)
                 fprintf(stderr, "[nanowrap] search_end: wait + copy-out of the staged result %ld us\n", (long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - tw0).count());
         } else if (by_flag && ctx->sliced_S > 0 && wait_block_done(ctx, ctx->sliced_base + 1)) {
             // the block's kernels have run and the slices are landing in the staging buffer: the copy threads take them as they come
@@ -1928,7 +1798,7 @@ NW_EXPORT int nw_search_end(nw_ctx *ctx, float *pos_out, nw_iter_log *log, int *
                 NW_HIP(hipStreamSynchronize(ctx->stream));           // (says what happened to the device, if anything)
                 return fail(ctx, NW_ERR_HIP, "the block's result did not arrive in the staging buffer");
             }
-            if (getenv("NW_VERBOSE") && atoi(getenv("NW_VERBOSE")) >= 3)
+            if (verbose_level() >= 3)
                 fprintf(stderr, "[nanowrap] search_end: %d slices through the flag word, copy-out %ld us after the last kernel\n", ctx->sliced_S, (long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - tw0).count());
         } else {
             const auto tw0 = std::chrono::steady_clock::now();
@@ -1937,7 +1807,7 @@ NW_EXPORT int nw_search_end(nw_ctx *ctx, float *pos_out, nw_iter_log *log, int *
                 NW_HIP(hipMemcpyAsync(stp, ctx->state.p, sizeof(NwDevState), hipMemcpyDeviceToHost, ctx->stream));
             }
             NW_TRY(write_back_impl(ctx, pos_out, ctx->wb_rows, ctx->wb_stride));
-            if (getenv("NW_VERBOSE") && atoi(getenv("NW_VERBOSE")) >= 3)
+            if (verbose_level() >= 3)
                 fprintf(stderr, "[nanowrap] search_end: wait + sliced write-back %ld us\n", (long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - tw0).count());
         }
     }
@@ -1945,7 +1815,7 @@ NW_EXPORT int nw_search_end(nw_ctx *ctx, float *pos_out, nw_iter_log *log, int *
     ctx->direct_out = false;
     ctx->done_launched = false; ctx->sliced_S = 0;
     NW_HIP(hipStreamSynchronize(ctx->stream));
-    if (getenv("NW_VERBOSE") && atoi(getenv("NW_VERBOSE")) >= 3)
+    if (verbose_level() >= 3)
         fprintf(stderr, "[nanowrap] search_end: final synchronize %ld us\n", (long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - ts0).count());
     const NwDevState st = *stp;
     int executed = 0;
@@ -2030,7 +1900,7 @@ static uint64_t block_graph_key(const nw_ctx *ctx)
 static int run_iteration(nw_ctx *ctx);
 static nw_ctx::BlockGraph *block_graph(nw_ctx *ctx, int num_iters, bool head)
 {
-    static const bool graphs_on = !(getenv("NW_GRAPH") && atoi(getenv("NW_GRAPH")) == 0);
+    static const bool graphs_on = env_on("NW_GRAPH");
     if (!(graphs_on && ctx->own_stream && (ctx->profiling == 0 || (head && ctx->profiling == 4)) && num_iters > (head ? 1 : 0))) return nullptr;
     if (ctx->search_done != 0) return nullptr;
     const uint64_t key = block_graph_key(ctx);
@@ -2230,7 +2100,7 @@ NW_EXPORT int nw_comm_all_reduce(nw_ctx *ctx, void *buf, int64_t count, int dtyp
 
 NW_EXPORT int nw_search(nw_ctx *ctx, const float *lams, int n_lams, int num_iters, uint32_t flags, float *pos_out, nw_iter_log *log, int *loopcount)
 {
-    const bool verbose = getenv("NW_VERBOSE") != nullptr && atoi(getenv("NW_VERBOSE")) >= 2;
+    const bool verbose = verbose_level() >= 2;
     const auto t0 = std::chrono::steady_clock::now();
     const uint32_t cmode = flags & (NW_FLAG_COMM_TILES | NW_FLAG_COMM_REPLICATED | NW_FLAG_COMM_HALO);
     if (ctx && cmode && !ctx->comm) return fail(ctx, NW_ERR_BADARG, "nw_search: NW_FLAG_COMM_* without a communicator (nw_comm_init)");
@@ -2243,7 +2113,7 @@ NW_EXPORT int nw_search(nw_ctx *ctx, const float *lams, int n_lams, int num_iter
     // warm/cold start).  Host-side enqueue drops from ~3.5 us per launch to one graph launch: what small meshes are bound by.
     // Not with per-launch profiling (levels 1, 2): events recorded by graph nodes do not give elapsed times on ROCm 7.2 (they read 0).
     // a host result comes back straight from the block's last update kernel (pinned staging buffer, then host threads copy it out)
-    static const bool direct_on = !(getenv("NW_DIRECT_OUT") && atoi(getenv("NW_DIRECT_OUT")) == 0);
+    static const bool direct_on = env_on("NW_DIRECT_OUT");
     ctx->direct_out = false;
     bool pos_on_device = false;
     if (pos_out && num_iters > 0) {
@@ -2262,7 +2132,7 @@ NW_EXPORT int nw_search(nw_ctx *ctx, const float *lams, int n_lams, int num_iter
     }
     ctx->last_direct_out = ctx->direct_out;
     bool replayed = false;
-    static const bool trace_blocks = getenv("NW_VERBOSE") != nullptr && atoi(getenv("NW_VERBOSE")) >= 3;
+    static const bool trace_blocks = verbose_level() >= 3;
     static hipEvent_t tb0 = nullptr, tb1 = nullptr;
     if (trace_blocks) { if (!tb0) { (void)hipEventCreate(&tb0); (void)hipEventCreate(&tb1); } (void)hipEventRecord(tb0, ctx->stream); }
     // level 4: the graph holds everything before the last iteration, which is launched below (its query kernel between two events)
@@ -2286,14 +2156,14 @@ NW_EXPORT int nw_search(nw_ctx *ctx, const float *lams, int n_lams, int num_iter
     }
     // NW_GRAPH_COMM=0: blocks with collectives are never recorded (every launch and every RCCL call issued directly, as in the first block of a
     // pattern) -- the fall-back if RCCL's kernels as graph nodes misbehave on some node; single-GPU blocks are not affected
-    static const bool graph_comm = !(getenv("NW_GRAPH_COMM") && atoi(getenv("NW_GRAPH_COMM")) == 0);
+    static const bool graph_comm = env_on("NW_GRAPH_COMM");
     if (!graph_comm && ctx->comm && ctx->comm_ranks > 1 && cmode) eager_first = true;
     // ... and the same by itself if recording such a block has failed twice (a capture that RCCL's calls invalidate is not an error of the
     // block: it runs directly; but trying again before every block would cost a failed capture each time)
     const bool comm_block = ctx->comm && ctx->comm_ranks > 1 && cmode;
     if (comm_block && ctx->comm_capture_failures >= 2) eager_first = true;
     nw_ctx::BlockGraph *slot = eager_first ? nullptr : block_graph(ctx, num_iters, head);
-    static const bool graphs_wanted = !(getenv("NW_GRAPH") && atoi(getenv("NW_GRAPH")) == 0);
+    static const bool graphs_wanted = env_on("NW_GRAPH");
     if (graphs_wanted && comm_block && !eager_first && !slot && ctx->own_stream && ctx->search_done == 0 && (ctx->profiling == 0 || (head && ctx->profiling == 4)) && num_iters > (head ? 1 : 0)) {
         if (++ctx->comm_capture_failures == 2)
             fprintf(stderr, "[nanowrap] a block with RCCL calls could not be recorded as a hipGraph (twice): such blocks are launched directly from now on (as with NW_GRAPH_COMM=0)\n");
@@ -2338,7 +2208,7 @@ NW_EXPORT int nw_search(nw_ctx *ctx, const float *lams, int n_lams, int num_iter
         NW_TRY(comm_all_reduce_dev(ctx, ctx->halo_full.p, (size_t)3 * ctx->M_global, ncclFloat, ncclSum));
         NW_HIP(hipMemsetAsync(ctx->halo_stats.p, 0, 4 * sizeof(float), ctx->stream));
         const int sblocks = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (ctx->M_global + NW_BLOCK - 1) / NW_BLOCK));
-        static const bool tail_direct = !(getenv("NW_HALO_TAIL_DIRECT") && atoi(getenv("NW_HALO_TAIL_DIRECT")) == 0);      // developer knob: 0 = a device-to-host copy behind the kernel
+        static const bool tail_direct = env_on("NW_HALO_TAIL_DIRECT");      // developer knob: 0 = a device-to-host copy behind the kernel
         hipLaunchKernelGGL(k_halo_block_stats, dim3(sblocks), dim3(NW_BLOCK), 0, ctx->stream, ctx->M_global, ctx->halo_full.p, ctx->halo_ref.p, 0.0f,
                            (float)ctx->local_quantum, ctx->halo_stats.p, (const NwIterLogDev *)ctx->logs.p, num_iters, tail_direct ? (float *)ctx->pin_full : (float *)nullptr);
         NW_HIP(hipGetLastError());
@@ -2472,6 +2342,22 @@ NW_EXPORT int nw_get(nw_ctx *ctx, int what, void *dst, int64_t nbytes)
     return NW_OK;
 }
 
+// the host threads that copy a result out (NW_HOST_THREADS of them, the caller included), and one event per thread for write_back_impl
+static int ensure_pool(nw_ctx *ctx)
+{
+    if (ctx->pool) return NW_OK;
+    int T = 8;
+    if (const char *e = getenv("NW_HOST_THREADS")) T = atoi(e);
+    const int hw = (int)std::thread::hardware_concurrency();
+    if (hw > 0 && T > hw) T = hw;
+    ctx->pool = new NwHostPool();
+    const int device = ctx->device;
+    ctx->pool->start(T, [device] { (void)hipSetDevice(device); });
+    ctx->wb_events.resize(ctx->pool->n);
+    for (auto &e : ctx->wb_events) NW_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return NW_OK;
+}
+
 // pinned staging buffer for a block's result (3 M floats) and the host threads that copy it out
 static int ensure_staging(nw_ctx *ctx)
 {
@@ -2485,17 +2371,7 @@ static int ensure_staging(nw_ctx *ctx)
         ctx->pin_sel = 0;
         ctx->pin = ctx->pin_base;
     }
-    if (!ctx->pool) {
-        int T = 8;
-        if (const char *e = getenv("NW_HOST_THREADS")) T = atoi(e);
-        const int hw = (int)std::thread::hardware_concurrency();
-        if (hw > 0 && T > hw) T = hw;
-        ctx->pool = new NwHostPool();
-        ctx->pool->start(T, ctx->device);
-        ctx->wb_events.resize(ctx->pool->n);
-        for (auto &e : ctx->wb_events) NW_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    return NW_OK;
+    return ensure_pool(ctx);
 }
 
 // the staging buffer already holds the result (written by the block's last kernel, stream synchronised): copy it out with the host threads
@@ -2506,55 +2382,11 @@ static void copy_out_staged(nw_ctx *ctx, float *contiguous, void *rows, int64_t 
     (void)copy_out_chunks(ctx, contiguous, rows, row_stride_bytes, 0, 0);
 }
 
-// The staged result -> the caller's arrays, in chunks of 8192 rows taken from a counter by the copy threads and the calling thread
-// (NwHostPool::run_chunks).  slice_rows > 0: the staging buffer is being filled slice by slice (k_copy_slice launches behind the block's
-// last kernel); the flag word reads flag_base + 1 + (slices complete), and a chunk waits for its slice.
+// the staged result -> the caller's arrays (nw_copy_out_chunks of nw_host_copy.h: what slice_rows and flag_base mean, and the deferred records)
 static bool copy_out_chunks(nw_ctx *ctx, float *contiguous, void *rows, int64_t row_stride_bytes, int64_t slice_rows, int flag_base)
 {
-    const int64_t M = ctx->M;
-    const float *stage = (const float *)ctx->pin;
-    const bool masked = rows && ctx->have_valid;
-    const unsigned char *vstage = masked ? ctx->valid_host.data() : nullptr;
-    const int64_t chunk = slice_rows > 0 ? std::max<int64_t>(4096, slice_rows / 2) : 8192;
-    const int nchunks = (int)((M + chunk - 1) / chunk);
-    volatile int *flag = ctx->pin_flag;
-    // NW_FLAG_ROWS_ASYNC: the contiguous result now, the strided records behind the caller's back (the pool's threads; nw_synchronize, the
-    // next block's copy-out and everything that touches the staging buffer or the records' description wait for them)
-    const bool defer_rows = ctx->rows_async && rows && ctx->pool && ctx->pool->n > 1;
-    std::atomic<bool> failed(false);
-    auto work = [&](int c) {
-        const int64_t v0 = (int64_t)c * chunk, v1 = std::min<int64_t>(M, v0 + chunk);
-        if (slice_rows > 0) {
-            const int need = flag_base + 1 + (int)((v1 - 1) / slice_rows) + 1;      // the chunk's last slice complete
-            long spins = 0;
-            const auto t0 = std::chrono::steady_clock::now();
-            while (*flag - need < 0 && !failed.load(std::memory_order_relaxed)) {
-                for (int k = 0; k < 8; ++k) __builtin_ia32_pause();
-                // (a slice is tens of microseconds of PCIe: seconds of silence mean the device is not going to answer)
-                if ((++spins & 4095) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(10)) failed = true;
-            }
-            if (failed.load()) return;
-        }
-        if (contiguous) memcpy(contiguous + 3 * v0, stage + 3 * v0, (size_t)(v1 - v0) * 12);
-        if (rows && !defer_rows) {
-            char *dst = (char *)rows;
-            for (int64_t v = v0; v < v1; ++v)
-                if (!masked || vstage[v]) memcpy(dst + v * row_stride_bytes, stage + 3 * v, 12);
-        }
-    };
-    if (!ctx->pool) { for (int c = 0; c < nchunks; ++c) work(c); return !failed.load(); }
-    if (contiguous || !defer_rows || slice_rows > 0) ctx->pool->run_chunks(nchunks, work);
-    if (failed.load()) return false;
-    if (defer_rows) {
-        char *dst = (char *)rows;
-        const int64_t rchunk = 8192;
-        ctx->pool->post_chunks((int)((M + rchunk - 1) / rchunk), [=](int c) {           // (by value: the job outlives this frame)
-            const int64_t v0 = (int64_t)c * rchunk, v1 = std::min<int64_t>(M, v0 + rchunk);
-            for (int64_t v = v0; v < v1; ++v)
-                if (!masked || vstage[v]) memcpy(dst + v * row_stride_bytes, stage + 3 * v, 12);
-        });
-    }
-    return true;
+    const unsigned char *valid = rows && ctx->have_valid ? ctx->valid_host.data() : nullptr;
+    return nw_copy_out_chunks((const float *)ctx->pin, ctx->M, contiguous, rows, row_stride_bytes, valid, ctx->pool, slice_rows, flag_base, ctx->pin_flag, ctx->rows_async);
 }
 
 static int write_back_impl(nw_ctx *ctx, float *contiguous, void *rows, int64_t row_stride_bytes)
@@ -2565,8 +2397,7 @@ static int write_back_impl(nw_ctx *ctx, float *contiguous, void *rows, int64_t r
     const int64_t M = ctx->M;
     NW_TRY(ensure_staging(ctx));
     float *stage = (float *)ctx->pin;
-    const bool masked = rows && ctx->have_valid;
-    const unsigned char *vstage = masked ? ctx->valid_host.data() : nullptr;
+    const unsigned char *valid = rows && ctx->have_valid ? ctx->valid_host.data() : nullptr;
     // The positions come back in T slices; slice t is copied out (contiguous result + strided vertex records) by host
     // thread t as soon as ITS part of the device-to-host transfer has landed, while the later slices are still in flight.
     static const int64_t rows_per_thread = getenv("NW_WB_ROWS_PER_THREAD") ? std::max(1000, atoi(getenv("NW_WB_ROWS_PER_THREAD"))) : 50000;   // measured: more, smaller slices lose to thread wake-up latency
@@ -2581,13 +2412,7 @@ static int write_back_impl(nw_ctx *ctx, float *contiguous, void *rows, int64_t r
     auto work = [&](int t) {
         if (t >= T) return;
         if (hipEventSynchronize(ctx->wb_events[t]) != hipSuccess) { failed = 1; return; }
-        const int64_t v0 = cut[t], v1 = cut[t + 1];
-        if (contiguous) memcpy(contiguous + 3 * v0, stage + 3 * v0, (size_t)(v1 - v0) * 12);
-        if (rows) {
-            char *dst = (char *)rows;
-            for (int64_t v = v0; v < v1; ++v)
-                if (!masked || vstage[v]) memcpy(dst + v * row_stride_bytes, stage + 3 * v, 12);
-        }
+        nw_copy_rows(stage, cut[t], cut[t + 1], contiguous, rows, row_stride_bytes, valid);
     };
     if (T == 1) work(0);
     else ctx->pool->run(work);
@@ -2611,28 +2436,13 @@ NW_EXPORT int nw_host_copy_rows(nw_ctx *ctx, const float *src, int64_t n_rows, f
         src = (const float *)ctx->pin_full;
     }
     if (rows && row_stride_bytes < 12) return fail(ctx, NW_ERR_BADARG, "nw_host_copy_rows: bad stride");
-    if (!ctx->pool) {
-        int T = 8;
-        if (const char *e = getenv("NW_HOST_THREADS")) T = atoi(e);
-        const int hw = (int)std::thread::hardware_concurrency();
-        if (hw > 0 && T > hw) T = hw;
-        ctx->pool = new NwHostPool();
-        ctx->pool->start(T, ctx->device);
-        ctx->wb_events.resize(ctx->pool->n);
-        for (auto &e : ctx->wb_events) NW_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
+    NW_TRY(ensure_pool(ctx));
     const int T = (int)std::max<int64_t>(1, std::min<int64_t>(ctx->pool->n, n_rows / rows_per_copy_thread()));
     auto work = [&](int t) {
         if (t >= T) return;
-        const int64_t v0 = n_rows * t / T, v1 = n_rows * (t + 1) / T;
-        if (contiguous) memcpy(contiguous + 3 * v0, src + 3 * v0, (size_t)(v1 - v0) * 12);
-        if (rows) {
-            char *dst = (char *)rows;
-            for (int64_t v = v0; v < v1; ++v)
-                if (!valid || valid[v]) memcpy(dst + v * row_stride_bytes, src + 3 * v, 12);
-        }
+        nw_copy_rows(src, n_rows * t / T, n_rows * (t + 1) / T, contiguous, rows, row_stride_bytes, valid);
     };
-    static const bool verbose3 = getenv("NW_VERBOSE") != nullptr && atoi(getenv("NW_VERBOSE")) >= 3;
+    static const bool verbose3 = verbose_level() >= 3;
     const auto tc0 = std::chrono::steady_clock::now();
     if (T == 1) work(0);
     else ctx->pool->run(work);
