@@ -1,7 +1,8 @@
 """
 GPU tests of the block-boundary remesher ON THE DEVICE (include/nanowrap.h: nw_remesh_device; csrc/nw_remesh_dev.hip),
-through the C-ABI.  PYME's TriangleMesh.remesh -- what the reference calls at _membrane_mesh.pyx:1546 -- is not in the reference tree, so there
-is nothing to be bit-exact with (parity unpinned); what is asserted is what makes a remeshing step correct and useful:
+through the C-ABI.  PYME's TriangleMesh.remesh -- what the reference calls at _membrane_mesh.pyx:1546 -- is not in the reference tree (parity
+with it is unpinned); bit for bit the kernels are compared with their own plain restatement in tests/test_hip_remesh_edges.py.  Here, on
+larger meshes, what is asserted is what makes a remeshing step correct and useful:
   * the result is a valid mesh of the same surface: every edge shared by exactly two faces (closed stays closed), the Euler characteristic
     kept (genus 0 and genus 2), vertex degrees within the limit, boundaries and their vertices untouched;
   * its statistics are the host remesher's (the same algorithm and admission tests, another order of operations): vertex count within 3 %,
