@@ -36,6 +36,7 @@ OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_BQ = _csrc('nanowrap.o'), _csrc('nw_ho
 OBJ_ISOSURFACE = _csrc('nw_isosurface.o')
 OBJ_EVALUATION = _csrc('nw_evaluation.o')
 OBJ_SIMULATION = _csrc('nw_simulation.o')
+OBJ_DISTANCE = _csrc('nw_distance.o')
 # the translation units of libnanowrap_hip.so: (source, object, what else it is rebuilt for, flags).  The objects are linked in this order.
 UNITS = [
     # the per-iteration kernels and the C-ABI; every header of csrc/ but nw_bq.h and nw_bq_core.h is included by it (directly or through
@@ -58,7 +59,10 @@ UNITS = [
     (_csrc('nw_evaluation.hip'), OBJ_EVALUATION, [_include('nw_evaluation.h'), _csrc('nw_evaluation_core.h')] + _BQ_H, _QUERY),
     # the SMLM cloud simulator: a shape's signed distance as a postfix program, the surface lattice, the localization model
     (_csrc('nw_simulation.hip'), OBJ_SIMULATION, [_include('nw_simulation.h')] + _BQ_H, _QUERY),
-    # what the five above share (csrc/nw_bq.h): the exclusive scan and the point grid's bounding box and counting sort, float and double
+    # the exact signed distance from points to the mesh (nw_distance_core.h: the point-triangle distance and the pseudonormals, which the
+    # tests also compile for the CPU)
+    (_csrc('nw_distance.hip'), OBJ_DISTANCE, [_include('nw_distance.h'), _csrc('nw_distance_core.h')] + _BQ_H, _QUERY),
+    # what the six above share (csrc/nw_bq.h): the exclusive scan and the point grid's bounding box and counting sort, float and double
     (_csrc('nw_bq.hip'), OBJ_BQ, _BQ, _QUERY),
 ]
 DEPS = sorted(set(d for src, _, extra, _ in UNITS for d in [src] + extra))
@@ -158,7 +162,12 @@ KERNEL_BUDGETS = {
     'k_sim_copy_equal':               (16, 0),
     'k_sim_copy_keep':                (16, 0),
     'k_sim_copy_emit':                (88, 0),             # three normals and three photon draws per copy, unrolled: 5 waves per SIMD
-    # what the five units above share (csrc/nw_bq.o): the exclusive scan, and the point grid of hole punching (f32) and of the metric (f64)
+    # the point-to-mesh distance (csrc/nw_distance.o): an end-of-fit query in float64, budgeted for zero scratch and against silent growth
+    'k_md_face_setup':                (64, 0),
+    'k_md_rho_reduce':                (24, 64),            # LDS = the four waves' maxima and sums
+    'k_md_query':                     (128, 64),           # float64 query, best record (d2, d, closest point, face, feature) and one exact test in flight: 4 waves per SIMD; LDS = the four waves' sums
+    'k_md_sum_final':                 (16, 64),
+    # what the six units above share (csrc/nw_bq.o): the exclusive scan, and the point grid of hole punching (f32) and of the metric (f64)
     'k_bq_scan_tiles':                (32, 1024),
     'k_bq_scan_bsums':                (32, 1024),
     'k_bq_scan_final':                (32, 1024),
@@ -169,7 +178,7 @@ KERNEL_BUDGETS = {
     'k_bq_cell_count_f64':            (48, 0),
     'k_bq_scatter_f64':               (16, 0),
 }
-BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_BQ]
+BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_DISTANCE, OBJ_BQ]
 
 
 def kernel_resources(obj=None):

@@ -465,6 +465,12 @@ class TriMesh(object):
     def area(self):
         return float(self._faces['area'].sum())
 
+    def signed_distance(self, points, **kw):
+        """The exact distance of every point from this mesh's triangles, negative inside: distance.distance_to_mesh(points, self, **kw)
+        (on the device; raises without a GPU)."""
+        from .distance import distance_to_mesh
+        return distance_to_mesh(points, self, **kw)
+
     # -- what upstream's MeshProperties module reads (evaluation.mesh_properties has the definitions).  None of them is a stored field:
     # each is computed from the face array when it is asked for and kept until the face array is replaced (a TriMesh's topology is
     # fixed: a remesher makes a new TriMesh).  euler and manifold are host work (twins and two connected-components passes, O(faces));
