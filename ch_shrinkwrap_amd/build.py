@@ -45,8 +45,9 @@ UNITS = [
      [f for f in HIPCC_FLAGS if f != '-shared']),
     # set-up radix sort (hipCUB)
     (_csrc('nw_sort.hip'), _csrc('nw_sort.o'), [], _BASE + ['-Wno-unused-value']),
-    # the block-boundary remesher as kernels (hipCUB scans)
-    (_csrc('nw_remesh_dev.hip'), _csrc('nw_remesh_dev.o'), [_include('nanowrap.h')],
+    # the block-boundary remesher as kernels (hipCUB scans; nw_remesh_plan.h: what its host driver decides, which the tests also compile
+    # for the CPU)
+    (_csrc('nw_remesh_dev.hip'), _csrc('nw_remesh_dev.o'), [_include('nanowrap.h'), _csrc('nw_remesh_plan.h')],
      _BASE + ['-ffp-contract=off', '-Wall', '-Wno-unused-value', '-Wno-unused-function']),
     # the hole-punch point queries
     (_csrc('nw_holepunch.hip'), OBJ_HOLEPUNCH, [_include('nw_holepunch.h')] + _BQ_H, _QUERY),

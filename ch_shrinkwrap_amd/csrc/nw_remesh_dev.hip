@@ -27,11 +27,15 @@
 // arithmetic, only the origin `F` and `twin` are stored; positions in float64 (as the host code); vhe[v] = one outgoing half-edge, val[v] =
 // degree, bnd[v] = vertex on an unmatched edge or a bow-tie: frozen.  A face that dies has F = -1.  Capacities are fixed per attempt from
 // the number of faces the edge lengths call for; an attempt that runs out reports it and the call starts again with twice the room.
+//
+// The host side, at the end of this file, is a driver in phases (struct Attempt: measure, load, iteration by iteration the passes, result).
+// What it decides between the launches -- the room of an attempt and how often it doubles, when a pass has run dry, when a split sweep is
+// left to the next iteration, when the iterations stop, the Morton cube of the input -- is plain C++ in nw_remesh_plan.h, which
+// tests/test_remesh_plan_cpu.py compiles for the CPU and holds against the restatement, tests/remesh_device_ref.py.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <cstdint>
 #include <cstdlib>
-#include <cstring>
 #include <cmath>
 #include <climits>
 #include <vector>
@@ -41,6 +45,7 @@
 #include <algorithm>
 
 #include "../../include/nanowrap.h"
+#include "nw_remesh_plan.h"
 
 #define NW_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -617,16 +622,20 @@ __global__ void k_rm_write_out(RM m, int nv, int nf, const int *__restrict__ fac
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------------
+// nw_remesh_device makes the device's Session current and runs Attempts with growing room.  An Attempt is its phases in order: measure()
+// the input and size the arrays, load() them and build the twins, iteration() (passes -- pass(kind): a candidate list, then rounds over it --
+// and relaxation), result(): compact, number and copy out.  What it decides between the launches is rm_plan's, nw_remesh_plan.h.
+//
 // Device memory of a call is carved out of two blocks that stay allocated between calls (a call makes some thirty arrays; hipMalloc and
 // hipFree of a few MB each took longer than the kernels).  A block grows to what the last call wanted; what does not fit is allocated
 // and freed the slow way.  The blocks, the stream and the pinned words belong to one device at a time and are guarded by g_lock (calls are
 // serialised).
 struct Cache { void *p = nullptr; size_t cap = 0, want = 0; };
-struct DevBuf {
+struct Arena {
     Cache &c;
     size_t used = 0;
     std::vector<void *> extra;
-    explicit DevBuf(Cache &cache) : c(cache)
+    explicit Arena(Cache &cache) : c(cache)
     {
         if (c.want > c.cap) {
             if (c.p) (void)hipFree(c.p);
@@ -646,7 +655,7 @@ struct DevBuf {
         extra.push_back(p);
         return (T *)p;
     }
-    ~DevBuf()
+    ~Arena()
     {
         for (void *p : extra) (void)hipFree(p);
         c.want = std::max(c.want, used);
@@ -661,269 +670,271 @@ struct Session {
 Session g_session;
 std::mutex g_lock;
 
-// (inside attempt(): an early exit first drains the stream -- asynchronous copies into this frame's arrays or the caller's vectors may be in flight)
-#define RM_RETURN(code) do { (void)hipStreamSynchronize(g_session.stream); return (code); } while (0)
-#define RM_HIP(x) do { if ((x) != hipSuccess) RM_RETURN(NW_ERR_HIP); } while (0)
+// (ways out of a phase.  Attempt::run drains the stream behind them: asynchronous copies land in members of the Attempt, never in a phase's locals)
+#define RM_HIP(x) do { if ((x) != hipSuccess) return NW_ERR_HIP; } while (0)
+#define RM_TRY(x) do { const int rc_ = (x); if (rc_ != NW_OK) return rc_; } while (0)
 #define RM_GRID(n) dim3((unsigned)(((n) + 255) / 256)), dim3(256)
-
 enum { RM_RETRY = 1 };        // an attempt ran out of room
-enum { ROUNDS_CAP = 4096 };   // rounds of one call (numbered through; a call that needs more stops early)
+using rm_plan::ROUNDS_CAP;
+static_assert(RC_COLLAPSE == RC_SPLIT + 1 && RC_FLIP == RC_SPLIT + 2, "rm_plan::iterations_end takes the three operation counters in a row");
+
+typedef std::chrono::steady_clock::time_point Time;
+static Time now() { return std::chrono::steady_clock::now(); }
+static double ms(Time a, Time b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+// a round's report in pinned memory: in within 2 s, or given up on
+static bool wait_for(const volatile int *report) { for (const Time t = now(); *report < 0 && ms(t, now()) < 2000.0;) {} return *report >= 0; }
 
 static int exclusive_scan(const int *in, int *out, int n, void *tmp, size_t tmp_bytes, hipStream_t s)
 {
     return hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, in, out, n, s) == hipSuccess ? NW_OK : NW_ERR_HIP;
 }
 
-static int attempt(const float *vertices, int64_t nv_in, const int32_t *faces, int64_t nf_in, int n_iterations, double L, double relax_lambda, int n_relax, int max_valence, double room,
-                   std::vector<float> &ov, std::vector<int32_t> &of, nw_remesh_stats *stats, bool verbose)
-{
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    const auto t0 = now();
-    hipStream_t st = g_session.stream;
-    DevBuf B(g_session.main);
-    const double high = 4.0 / 3.0 * L, low = 4.0 / 5.0 * L;
-    // inputs on the device, the number of faces the lengths call for
-    float *d_vin = B.get<float>(3 * (size_t)nv_in);
-    int *d_fin = B.get<int>(3 * (size_t)nf_in);
-    int *d_cnt = B.get<int>(RC_COUNT);
-    const int nblk_f = (int)((nf_in + 255) / 256);
-    double *d_part0 = B.get<double>((size_t)nblk_f);
-    if (!d_vin || !d_fin || !d_cnt || !d_part0) RM_RETURN(NW_ERR_NOMEM);
-    RM_HIP(hipMemcpyAsync(d_vin, vertices, sizeof(float) * 3 * (size_t)nv_in, hipMemcpyHostToDevice, st));
-    RM_HIP(hipMemcpyAsync(d_fin, faces, sizeof(int) * 3 * (size_t)nf_in, hipMemcpyHostToDevice, st));
-    RM_HIP(hipMemsetAsync(d_cnt, 0, sizeof(int) * RC_COUNT, st));
-    // a first, small mesh record just to measure the input (positions + faces)
+// what a call is given, the same for every attempt (verbose: 0 without NWR_VERBOSE, 2 for a value of 2 or more, else 1)
+struct Input {
+    const float *vertices; int64_t nv; const int32_t *faces; int64_t nf;
+    int n_iterations; double L, relax_lambda; int n_relax, max_valence; rm_plan::Cube cube; int verbose;
+};
+// what a call hands out, malloc'ed: freed here unless the caller has been given it
+struct Output { float *v = nullptr; int32_t *f = nullptr; int64_t nv = 0, nf = 0; ~Output() { std::free(v); std::free(f); } };
+
+struct Attempt {
+    const Input &in;
+    hipStream_t st; int *h_cand;   // the session's
+    // main: the mesh and what lives as long; temp: the measuring copy, the hash table, the lists, the reports and the result's arrays.
+    // Both last as long as the attempt.
+    Arena main, temp;
     RM m{};
-    m.cnt = d_cnt; m.max_valence = max_valence; m.high2 = high * high; m.low2 = low * low;
-    // capacity is decided after the pieces are counted; the load needs pos / F / vhe / val / bnd of the input's size at least, so the
-    // count runs on temporaries of that size
+    rm_plan::Capacity cap{};
+    float *d_vin = nullptr; int *d_fin = nullptr, *d_cnt = nullptr;
+    void *d_tmp = nullptr; size_t tmp_bytes = 0;      // scratch of the scans
+    int *d_list = nullptr, *d_list2 = nullptr; D3 *d_upd = nullptr;
+    int nv = 0, nf = 0;            // vertex and face slots in use (the splits move them)
+    int rounds[3] = {0, 0, 0}; unsigned round_id = 0, pass_seq = 0;
+    Time t0, t1, t2;
+    int cnt[RC_COUNT]; std::vector<double> sums; int n_out[2];      // where asynchronous copies land: counters, block sums, the result's sizes
+    explicit Attempt(const Input &input) : in(input), st(g_session.stream), h_cand(g_session.h_cand), main(g_session.main), temp(g_session.temp), t0(now()) {}
+    int read_counters()            // -> cnt
     {
-        DevBuf T(g_session.temp);
-        RM t = m;
-        t.pos = T.get<D3>((size_t)nv_in); t.F = T.get<int>(3 * (size_t)nf_in); t.vhe = T.get<int>((size_t)nv_in); t.val = T.get<int>((size_t)nv_in);
-        t.bnd = T.get<unsigned char>((size_t)nv_in);
-        if (!t.pos || !t.F || !t.vhe || !t.val || !t.bnd) RM_RETURN(NW_ERR_NOMEM);
-        hipLaunchKernelGGL(k_rm_load, RM_GRID(std::max(nv_in, nf_in)), 0, st, d_vin, (int)nv_in, d_fin, (int)nf_in, t);
-        hipLaunchKernelGGL(k_rm_pieces, dim3(nblk_f), dim3(256), 0, st, t, (int)nf_in, high, d_part0);
-        std::vector<double> part((size_t)nblk_f);
-        int cnt[RC_COUNT];
-        RM_HIP(hipMemcpyAsync(part.data(), d_part0, sizeof(double) * (size_t)nblk_f, hipMemcpyDeviceToHost, st));
         RM_HIP(hipMemcpyAsync(cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, st));
-        RM_HIP(hipStreamSynchronize(st));
-        if (cnt[RC_BADARG]) RM_RETURN(NW_ERR_BADARG);
-        double pieces = 0.0;
-        for (double p : part) pieces += p;
-        if (!(pieces < 67108864.0)) RM_RETURN(NW_ERR_BADARG);                      // (the host code's "runaway": a vertex flung far away)
-        m.high2 = high * high;
-        // room for the faces: what the lengths call for (or the input, if that is more), times `room`
-        const double want = std::max(pieces, (double)nf_in) * room + 8192.0;
-        if (want > 5.0e8) RM_RETURN(NW_ERR_NOMEM);
-        const size_t Fcap = (size_t)want, Vcap = (size_t)nv_in + (Fcap - (size_t)nf_in) / 2 + 1024, Hcap = 3 * Fcap;
-        m.pos = B.get<D3>(Vcap); m.F = B.get<int>(Hcap); m.twin = B.get<int>(Hcap); m.vhe = B.get<int>(Vcap); m.val = B.get<int>(Vcap);
-        m.bnd = B.get<unsigned char>(Vcap); m.owner = B.get<u64>(Vcap); m.ckey = B.get<u64>(Hcap); m.win = B.get<int>(Hcap); m.scan = B.get<int>(Hcap);
-        if (!m.pos || !m.F || !m.twin || !m.vhe || !m.val || !m.bnd || !m.owner || !m.ckey || !m.win || !m.scan) RM_RETURN(NW_ERR_NOMEM);
-        size_t tmp_bytes = 0;
-        if (hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, m.win, m.scan, (int)Hcap, st) != hipSuccess) RM_RETURN(NW_ERR_HIP);
-        void *d_tmp = B.get<unsigned char>(tmp_bytes + 16);
-        if (!d_tmp) RM_RETURN(NW_ERR_NOMEM);
-        hipLaunchKernelGGL(k_rm_load, RM_GRID(std::max(nv_in, nf_in)), 0, st, d_vin, (int)nv_in, d_fin, (int)nf_in, m);
-        // twins through a hash table of the directed edges
+        return hipStreamSynchronize(st) == hipSuccess ? NW_OK : NW_ERR_HIP;
+    }
+
+    // inputs on the device, the number of faces the lengths call for, the capacities
+    int measure(double room)
+    {
+        const double high = rm_plan::edge_high(in.L), low = rm_plan::edge_low(in.L);
+        d_vin = main.get<float>(3 * (size_t)in.nv); d_fin = main.get<int>(3 * (size_t)in.nf); d_cnt = main.get<int>(RC_COUNT);
+        const int nblk_f = (int)((in.nf + 255) / 256); double *d_part = main.get<double>((size_t)nblk_f);
+        if (!d_vin || !d_fin || !d_cnt || !d_part) return NW_ERR_NOMEM;
+        RM_HIP(hipMemcpyAsync(d_vin, in.vertices, sizeof(float) * 3 * (size_t)in.nv, hipMemcpyHostToDevice, st));
+        RM_HIP(hipMemcpyAsync(d_fin, in.faces, sizeof(int) * 3 * (size_t)in.nf, hipMemcpyHostToDevice, st));
+        RM_HIP(hipMemsetAsync(d_cnt, 0, sizeof(int) * RC_COUNT, st));
+        m.cnt = d_cnt; m.max_valence = in.max_valence; m.high2 = high * high; m.low2 = low * low;
+        // capacity is decided after the pieces are counted; the load needs pos / F / vhe / val / bnd of the input's size at least, so the
+        // count runs on a first, small mesh record of that size: temporaries, just to measure the input
+        RM t = m;
+        t.pos = temp.get<D3>((size_t)in.nv); t.F = temp.get<int>(3 * (size_t)in.nf); t.vhe = temp.get<int>((size_t)in.nv); t.val = temp.get<int>((size_t)in.nv);
+        t.bnd = temp.get<unsigned char>((size_t)in.nv);
+        if (!t.pos || !t.F || !t.vhe || !t.val || !t.bnd) return NW_ERR_NOMEM;
+        hipLaunchKernelGGL(k_rm_load, RM_GRID(std::max(in.nv, in.nf)), 0, st, d_vin, (int)in.nv, d_fin, (int)in.nf, t);
+        hipLaunchKernelGGL(k_rm_pieces, dim3(nblk_f), dim3(256), 0, st, t, (int)in.nf, high, d_part);
+        sums.resize((size_t)nblk_f);
+        RM_HIP(hipMemcpyAsync(sums.data(), d_part, sizeof(double) * (size_t)nblk_f, hipMemcpyDeviceToHost, st));
+        RM_TRY(read_counters());
+        if (cnt[RC_BADARG]) return NW_ERR_BADARG;
+        double pieces = 0.0;                        // (block sums, added in block order)
+        for (double p : sums) pieces += p;
+        const rm_plan::Fit fit = rm_plan::capacities(pieces, in.nv, in.nf, room, &cap);
+        return fit == rm_plan::FITS ? NW_OK : fit == rm_plan::RUNAWAY ? NW_ERR_BADARG : NW_ERR_NOMEM;
+    }
+
+    // the mesh record at its capacities: the input, twins through a hash table of the directed edges, the vertex flags; then what the rounds need
+    int load()
+    {
+        const size_t Vcap = cap.Vcap, Hcap = cap.Hcap;
+        m.pos = main.get<D3>(Vcap); m.F = main.get<int>(Hcap); m.twin = main.get<int>(Hcap); m.vhe = main.get<int>(Vcap); m.val = main.get<int>(Vcap);
+        m.bnd = main.get<unsigned char>(Vcap); m.owner = main.get<u64>(Vcap); m.ckey = main.get<u64>(Hcap); m.win = main.get<int>(Hcap); m.scan = main.get<int>(Hcap);
+        if (!m.pos || !m.F || !m.twin || !m.vhe || !m.val || !m.bnd || !m.owner || !m.ckey || !m.win || !m.scan) return NW_ERR_NOMEM;
+        // (the one scan call that does not go through exclusive_scan: from `int *` it names a rocPRIM instantiation of its own, which is never
+        // launched; it stays for now so that this unit's device code object is byte for byte what it was before the driver was put in phases)
+        if (hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, m.win, m.scan, (int)Hcap, st) != hipSuccess) return NW_ERR_HIP;
+        if (!(d_tmp = main.get<unsigned char>(tmp_bytes + 16))) return NW_ERR_NOMEM;
+        hipLaunchKernelGGL(k_rm_load, RM_GRID(std::max(in.nv, in.nf)), 0, st, d_vin, (int)in.nv, d_fin, (int)in.nf, m);
         unsigned hcap = 1;
-        while (hcap < 2 * 3 * (size_t)nf_in) hcap <<= 1;
-        u64 *d_keys = T.get<u64>(hcap);
-        int *d_vals = T.get<int>(hcap);
-        if (!d_keys || !d_vals) RM_RETURN(NW_ERR_NOMEM);
+        while (hcap < 2 * 3 * (size_t)in.nf) hcap <<= 1;
+        u64 *d_keys = temp.get<u64>(hcap); int *d_vals = temp.get<int>(hcap);
+        if (!d_keys || !d_vals) return NW_ERR_NOMEM;
         RM_HIP(hipMemsetAsync(d_keys, 0xff, sizeof(u64) * hcap, st));
-        const int nh_in = (int)(3 * nf_in);
+        const int nh_in = (int)(3 * in.nf);
         hipLaunchKernelGGL(k_rm_hash_insert, RM_GRID(nh_in), 0, st, m, nh_in, d_keys, d_vals, hcap - 1);
         hipLaunchKernelGGL(k_rm_hash_lookup, RM_GRID(nh_in), 0, st, m, nh_in, d_keys, d_vals, hcap - 1);
-        hipLaunchKernelGGL(k_rm_vertex_flags, RM_GRID(nv_in), 0, st, m, (int)nv_in);
-        RM_HIP(hipMemcpyAsync(cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, st));
-        RM_HIP(hipStreamSynchronize(st));
-        if (cnt[RC_NONMANIFOLD]) RM_RETURN(NW_ERR_NONMANIFOLD);
-        const auto t1 = now();
-
+        hipLaunchKernelGGL(k_rm_vertex_flags, RM_GRID(in.nv), 0, st, m, (int)in.nv);
+        RM_TRY(read_counters());
+        if (cnt[RC_NONMANIFOLD]) return NW_ERR_NONMANIFOLD;
+        t1 = now();
         // sizes live on the device from here on (the splits move them); the host reads them where it needs a grid size
-        int *d_list = T.get<int>(Hcap / 2 + 64), *d_list2 = T.get<int>(Hcap / 2 + 64);
-        D3 *d_upd = n_relax > 0 ? T.get<D3>(Vcap) : nullptr;
-        if (!d_list || !d_list2 || (n_relax > 0 && !d_upd)) RM_RETURN(NW_ERR_NOMEM);
-        {
-            int init[RC_COUNT] = {0};
-            init[RC_NV] = (int)nv_in; init[RC_NF] = (int)nf_in; init[RC_VCAP] = (int)Vcap; init[RC_FCAP] = (int)Fcap;
-            RM_HIP(hipMemcpyAsync(d_cnt, init, sizeof(init), hipMemcpyHostToDevice, st));
-            RM_HIP(hipStreamSynchronize(st));
-        }
+        d_list = temp.get<int>(cap.list); d_list2 = temp.get<int>(cap.list); d_upd = in.n_relax > 0 ? temp.get<D3>(Vcap) : nullptr;
+        if (!d_list || !d_list2 || (in.n_relax > 0 && !d_upd)) return NW_ERR_NOMEM;
+        int init[RC_COUNT] = {0};
+        init[RC_NV] = (int)in.nv; init[RC_NF] = (int)in.nf; init[RC_VCAP] = (int)Vcap; init[RC_FCAP] = (int)cap.Fcap;
+        RM_HIP(hipMemcpyAsync(d_cnt, init, sizeof(init), hipMemcpyHostToDevice, st));
+        RM_HIP(hipStreamSynchronize(st));
         // rounds are numbered through the whole call; how many candidates bid in a round is written to pinned host memory by the round's
         // apply kernel, so the host -- a round or two ahead with its launches -- sees a pass run dry without waiting for anything
-        m.round_cand = T.get<int>(ROUNDS_CAP);
-        int *h_cand = g_session.h_cand;
+        m.round_cand = temp.get<int>(ROUNDS_CAP); m.host_cand = h_cand;
         for (int i = 0; i < ROUNDS_CAP; ++i) h_cand[i] = -1;
-        m.host_cand = h_cand;
-        if (!m.round_cand) RM_RETURN(NW_ERR_NOMEM);
+        if (!m.round_cand) return NW_ERR_NOMEM;
         RM_HIP(hipMemsetAsync(m.round_cand, 0, sizeof(int) * ROUNDS_CAP, st));
         RM_HIP(hipMemsetAsync(m.owner, 0, sizeof(u64) * Vcap, st));
-        int nv = (int)nv_in, nf = (int)nf_in;
-        int rounds[3] = {0, 0, 0};
-        unsigned round_id = 0, pass_seq = 0;
-        auto read_cnt = [&](int *c) -> int {
-            if (hipMemcpyAsync(c, d_cnt, sizeof(int) * RC_COUNT, hipMemcpyDeviceToHost, st) != hipSuccess) RM_RETURN(NW_ERR_HIP);
-            return hipStreamSynchronize(st) == hipSuccess ? NW_OK : NW_ERR_HIP;
-        };
-        // one pass of one kind: the candidate list from a scan over all half-edges, then rounds over the list.  Returns the list's length.
-        const int R_MAX[3] = {24, 32, 24};
-        auto pass = [&](int kind, int *n_list_out) -> int {
-            const int nh = 3 * nf;
-            if (kind == 0) hipLaunchKernelGGL(k_rm_candidates<0>, RM_GRID(nh), 0, st, m, m.win);
-            else if (kind == 1) hipLaunchKernelGGL(k_rm_candidates<1>, RM_GRID(nh), 0, st, m, m.win);
-            else hipLaunchKernelGGL(k_rm_candidates<2>, RM_GRID(nh), 0, st, m, m.win);
-            if (exclusive_scan(m.win, m.scan, nh, d_tmp, tmp_bytes, st) != NW_OK) RM_RETURN(NW_ERR_HIP);
-            hipLaunchKernelGGL(k_rm_compact, RM_GRID(nh), 0, st, m, m.win, m.scan, d_list);
-            int c[RC_COUNT];
-            if (read_cnt(c) != NW_OK) RM_RETURN(NW_ERR_HIP);
-            const int n = c[RC_NLIST];
-            *n_list_out = n;
-            if (n == 0) return NW_OK;
-            if ((size_t)n > Hcap / 2 + 64) RM_RETURN(NW_ERR_INTERNAL);
-            const unsigned first = round_id + 1;
-            const unsigned pass_no = ++pass_seq;
-            const int *list = d_list;
-            int first_bids = -1;
-            for (int r = 0; r < R_MAX[kind]; ++r) {
-                // The host may run at most two rounds ahead of the GPU's reports: it waits (a spin on pinned memory) for the count of the round
-                // before last, and stops the pass when a reported round had no bidder -- or so few that the next iteration may as well
-                // have them (a tail of a handful of candidates that keep losing to each other took as many rounds as all the others).
-                if (r >= 2) {
-                    const volatile int *w = h_cand + (first + (unsigned)r - 2);
-                    const auto t_w = now();
-                    while (*w < 0 && ms(t_w, now()) < 2000.0) {}
-                    if (*w < 0) RM_RETURN(NW_ERR_INTERNAL);
+        nv = (int)in.nv; nf = (int)in.nf;
+        return NW_OK;
+    }
+
+    // one pass of one kind: the candidate list from a scan over all half-edges, then rounds over the list.  *n_list: the list's length.
+    int pass(int kind, int *n_list)
+    {
+        static void (*const candidates[3])(RM, int *) = {k_rm_candidates<0>, k_rm_candidates<1>, k_rm_candidates<2>};      // split, collapse, flip
+        const int nh = 3 * nf;
+        hipLaunchKernelGGL(candidates[kind], RM_GRID(nh), 0, st, m, m.win);
+        RM_TRY(exclusive_scan(m.win, m.scan, nh, d_tmp, tmp_bytes, st));
+        hipLaunchKernelGGL(k_rm_compact, RM_GRID(nh), 0, st, m, m.win, m.scan, d_list);
+        RM_TRY(read_counters());
+        const int n = *n_list = cnt[RC_NLIST];
+        if (n == 0) return NW_OK;
+        if ((size_t)n > cap.list) return NW_ERR_INTERNAL;
+        const unsigned first = round_id + 1, pass_no = ++pass_seq;
+        const volatile int *reports = h_cand + first;         // of this pass's rounds
+        const int *list = d_list;
+        for (int r = 0; r < rm_plan::R_MAX[kind]; ++r) {
+            // The host may run at most two rounds ahead of the GPU's reports: it waits (a spin on pinned memory) for the count of the round
+            // before last, and then asks whether the pass has run dry (rm_plan::launches_round)
+            if (r >= rm_plan::RUN_AHEAD && !wait_for(reports + (r - rm_plan::RUN_AHEAD))) return NW_ERR_INTERNAL;
+            if (!rm_plan::launches_round(reports, r, first)) break;
+            const unsigned round = ++round_id, seed = rm_plan::round_seed(pass_no, r);
+            if (kind == 0) {
+                hipLaunchKernelGGL(k_rm_split_bid, RM_GRID(n), 0, st, m, list, round, seed);
+                hipLaunchKernelGGL(k_rm_split_mark, RM_GRID(n), 0, st, m, list);
+                RM_TRY(exclusive_scan(m.win, m.scan, n, d_tmp, tmp_bytes, st));
+                hipLaunchKernelGGL(k_rm_split_apply, RM_GRID(n), 0, st, m, list);
+                hipLaunchKernelGGL(k_rm_split_commit, dim3(1), dim3(1), 0, st, m, round);
+            } else if (kind == 1) {
+                hipLaunchKernelGGL(k_rm_collapse_bid, RM_GRID(n), 0, st, m, list, round, seed, r == 0 ? m.win : (int *)nullptr);
+                hipLaunchKernelGGL(k_rm_collapse_apply, RM_GRID(n), 0, st, m, list, round);
+                if (r == 0) {
+                    RM_TRY(exclusive_scan(m.win, m.scan, n, d_tmp, tmp_bytes, st));
+                    hipLaunchKernelGGL(k_rm_relist, RM_GRID(n), 0, st, m, list, m.win, m.scan, d_list2);
+                    hipLaunchKernelGGL(k_rm_relist_commit, dim3(1), dim3(1), 0, st, m, m.win, m.scan);
+                    list = d_list2;
                 }
-                bool dry = false;
-                // (an empty round may be noticed whenever its report happens to be in -- the rounds behind it do nothing either way --, but the
-                // "so few" rule decides whether real work is done: it looks at the round before last only, whose report the host has waited for)
-                for (unsigned k = first; k <= round_id; ++k) {
-                    const int b = *(volatile int *)(h_cand + k);
-                    if (k == first && b >= 0) first_bids = b;
-                    dry = dry || b == 0 || (r >= 2 && k + 2 <= first + (unsigned)r && b > 0 && first_bids > 0 && b < 8 && b * 500 < first_bids);
-                }
-                if (dry || round_id + 1 >= (unsigned)ROUNDS_CAP) break;
-                const unsigned round = ++round_id, seed = pass_no * 64u + (unsigned)r;
-                if (kind == 0) {
-                    hipLaunchKernelGGL(k_rm_split_bid, RM_GRID(n), 0, st, m, list, round, seed);
-                    hipLaunchKernelGGL(k_rm_split_mark, RM_GRID(n), 0, st, m, list);
-                    if (exclusive_scan(m.win, m.scan, n, d_tmp, tmp_bytes, st) != NW_OK) RM_RETURN(NW_ERR_HIP);
-                    hipLaunchKernelGGL(k_rm_split_apply, RM_GRID(n), 0, st, m, list);
-                    hipLaunchKernelGGL(k_rm_split_commit, dim3(1), dim3(1), 0, st, m, round);
-                } else if (kind == 1) {
-                    hipLaunchKernelGGL(k_rm_collapse_bid, RM_GRID(n), 0, st, m, list, round, seed, r == 0 ? m.win : (int *)nullptr);
-                    hipLaunchKernelGGL(k_rm_collapse_apply, RM_GRID(n), 0, st, m, list, round);
-                    if (r == 0) {
-                        if (exclusive_scan(m.win, m.scan, n, d_tmp, tmp_bytes, st) != NW_OK) RM_RETURN(NW_ERR_HIP);
-                        hipLaunchKernelGGL(k_rm_relist, RM_GRID(n), 0, st, m, list, m.win, m.scan, d_list2);
-                        hipLaunchKernelGGL(k_rm_relist_commit, dim3(1), dim3(1), 0, st, m, m.win, m.scan);
-                        list = d_list2;
-                    }
-                } else {
-                    hipLaunchKernelGGL(k_rm_flip_bid, RM_GRID(n), 0, st, m, list, round, seed);
-                    hipLaunchKernelGGL(k_rm_flip_apply, RM_GRID(n), 0, st, m, list, round);
-                }
-                ++rounds[kind];
+            } else {
+                hipLaunchKernelGGL(k_rm_flip_bid, RM_GRID(n), 0, st, m, list, round, seed);
+                hipLaunchKernelGGL(k_rm_flip_apply, RM_GRID(n), 0, st, m, list, round);
             }
-            if (std::getenv("NWR_VERBOSE") && std::atoi(std::getenv("NWR_VERBOSE")) >= 2) {
-                (void)hipStreamSynchronize(st);
-                std::fprintf(stderr, "[nw_remesh_device]     kind %d: list %d, bids per round:", kind, n);
-                for (unsigned k = first; k <= round_id; ++k) std::fprintf(stderr, " %d", h_cand[k]);
-                std::fprintf(stderr, "\n");
-            }
-            return NW_OK;
-        };
-        for (int it = 0; it < n_iterations; ++it) {
-            int before[RC_COUNT], c[RC_COUNT], n_list = 0, rc;
-            if (read_cnt(before) != NW_OK) RM_RETURN(NW_ERR_HIP);
-            // split: what a pass creates is looked at by the next one (the host code's sweeps: up to 8)
-            int first_list = 0;
-            for (int sub = 0; sub < 4; ++sub) {
-                if ((rc = pass(0, &n_list)) != NW_OK) RM_RETURN(rc);
-                if (n_list == 0) break;
-                if (sub == 0) first_list = n_list;
-                if (read_cnt(c) != NW_OK) RM_RETURN(NW_ERR_HIP);
-                if (c[RC_OVERFLOW]) RM_RETURN(RM_RETRY);
-                nv = c[RC_NV]; nf = c[RC_NF];
-                // (what the splits of a sweep leave too long is the next sweep's; a sweep over a handful of edges -- a scan over all half-edges, a
-                // compaction and a few rounds for six edges of 4 10^5 -- is left to the next iteration, as the rounds' tails are)
-                if (n_list < 32 && n_list * 200 < first_list) break;
-            }
-            if ((rc = pass(1, &n_list)) != NW_OK) RM_RETURN(rc);
-            if ((rc = pass(2, &n_list)) != NW_OK) RM_RETURN(rc);
-            for (int k = 0; k < n_relax; ++k) {
-                hipLaunchKernelGGL(k_rm_relax, RM_GRID(nv), 0, st, m, relax_lambda, d_upd);
-                hipLaunchKernelGGL(k_rm_relax_commit, RM_GRID(nv), 0, st, m, d_upd);
-            }
-            if (read_cnt(c) != NW_OK) RM_RETURN(NW_ERR_HIP);
-            if (c[RC_CORRUPT]) RM_RETURN(NW_ERR_INTERNAL);
-            if (verbose) std::fprintf(stderr, "[nw_remesh_device] iteration %d: %d / %d / %d operations so far, %d vertex slots, %d face slots; rounds so far %d / %d / %d\n", it,
-                                      c[RC_SPLIT], c[RC_COLLAPSE], c[RC_FLIP], nv, nf, rounds[0], rounds[1], rounds[2]);
-            // a pass that changed nothing would be repeated unchanged by every later iteration
-            if (n_relax == 0 && c[RC_SPLIT] == before[RC_SPLIT] && c[RC_COLLAPSE] == before[RC_COLLAPSE] && c[RC_FLIP] == before[RC_FLIP]) break;      // (with relaxation every vertex moves: the next iteration sees another mesh)
+            ++rounds[kind];
         }
-        const auto t2 = now();
-        // compact: faces that are alive, vertices they refer to (relative order kept)
-        int *d_alive = T.get<int>((size_t)nf + 1), *d_face_at = T.get<int>((size_t)nf + 1), *d_used = T.get<int>((size_t)nv + 1), *d_vert_at = T.get<int>((size_t)nv + 1);
-        const int nblk = (std::max(nv, nf) + 255) / 256;
-        double *d_part = T.get<double>((size_t)nblk);
-        if (!d_alive || !d_face_at || !d_used || !d_vert_at || !d_part) RM_RETURN(NW_ERR_NOMEM);
+        if (in.verbose >= 2) {
+            (void)hipStreamSynchronize(st);
+            std::fprintf(stderr, "[nw_remesh_device]     kind %d: list %d, bids per round:", kind, n);
+            for (unsigned k = first; k <= round_id; ++k) std::fprintf(stderr, " %d", h_cand[k]);
+            std::fprintf(stderr, "\n");
+        }
+        return NW_OK;
+    }
+
+    // split sweeps, a collapse pass, a flip pass, the relaxation.  *last: no later iteration would change anything.
+    int iteration(int it, bool *last)
+    {
+        int n_list = 0, first_list = 0;
+        RM_TRY(read_counters());
+        const int before[3] = {cnt[RC_SPLIT], cnt[RC_COLLAPSE], cnt[RC_FLIP]};
+        // split: what a pass creates is looked at by the next one (rm_plan::SPLIT_SWEEPS, rm_plan::sweeps_end)
+        for (int sub = 0; sub < rm_plan::SPLIT_SWEEPS; ++sub) {
+            RM_TRY(pass(0, &n_list));
+            if (n_list == 0) break;
+            if (sub == 0) first_list = n_list;
+            RM_TRY(read_counters());
+            if (cnt[RC_OVERFLOW]) return RM_RETRY;
+            nv = cnt[RC_NV]; nf = cnt[RC_NF];
+            if (rm_plan::sweeps_end(n_list, first_list)) break;
+        }
+        RM_TRY(pass(1, &n_list));
+        RM_TRY(pass(2, &n_list));
+        for (int k = 0; k < in.n_relax; ++k) {
+            hipLaunchKernelGGL(k_rm_relax, RM_GRID(nv), 0, st, m, in.relax_lambda, d_upd);
+            hipLaunchKernelGGL(k_rm_relax_commit, RM_GRID(nv), 0, st, m, d_upd);
+        }
+        RM_TRY(read_counters());
+        if (cnt[RC_CORRUPT]) return NW_ERR_INTERNAL;
+        if (in.verbose) std::fprintf(stderr, "[nw_remesh_device] iteration %d: %d / %d / %d operations so far, %d vertex slots, %d face slots; rounds so far %d / %d / %d\n", it,
+                                     cnt[RC_SPLIT], cnt[RC_COLLAPSE], cnt[RC_FLIP], nv, nf, rounds[0], rounds[1], rounds[2]);
+        *last = rm_plan::iterations_end(in.n_relax, before, cnt + RC_SPLIT);
+        return NW_OK;
+    }
+
+    // compact: faces that are alive, vertices they refer to (relative order kept) in Morton order; straight into the arrays the call hands out
+    int result(Output *out, nw_remesh_stats *stats)
+    {
+        int *d_alive = temp.get<int>((size_t)nf + 1), *d_face_at = temp.get<int>((size_t)nf + 1), *d_used = temp.get<int>((size_t)nv + 1), *d_vert_at = temp.get<int>((size_t)nv + 1);
+        const int nblk = (std::max(nv, nf) + 255) / 256; double *d_part = temp.get<double>((size_t)nblk);
+        if (!d_alive || !d_face_at || !d_used || !d_vert_at || !d_part) return NW_ERR_NOMEM;
         RM_HIP(hipMemsetAsync(d_used, 0, sizeof(int) * ((size_t)nv + 1), st));
         RM_HIP(hipMemsetAsync(d_alive + nf, 0, sizeof(int), st));
         hipLaunchKernelGGL(k_rm_mark_used, RM_GRID(nf), 0, st, m, nf, d_alive, d_used);
-        if (exclusive_scan(d_alive, d_face_at, nf + 1, d_tmp, tmp_bytes, st) != NW_OK) RM_RETURN(NW_ERR_HIP);
-        if (exclusive_scan(d_used, d_vert_at, nv + 1, d_tmp, tmp_bytes, st) != NW_OK) RM_RETURN(NW_ERR_HIP);
-        int n_out[2];
+        RM_TRY(exclusive_scan(d_alive, d_face_at, nf + 1, d_tmp, tmp_bytes, st));
+        RM_TRY(exclusive_scan(d_used, d_vert_at, nv + 1, d_tmp, tmp_bytes, st));
         RM_HIP(hipMemcpyAsync(&n_out[0], d_face_at + nf, sizeof(int), hipMemcpyDeviceToHost, st));
         RM_HIP(hipMemcpyAsync(&n_out[1], d_vert_at + nv, sizeof(int), hipMemcpyDeviceToHost, st));
         RM_HIP(hipStreamSynchronize(st));
         const int nf_out = n_out[0], nv_out = n_out[1];
-        float *d_ov = T.get<float>(3 * (size_t)nv_out);
-        int *d_of = T.get<int>(3 * (size_t)nf_out);
-        unsigned *d_key = T.get<unsigned>((size_t)nv_out), *d_key2 = T.get<unsigned>((size_t)nv_out);
-        int *d_idx = T.get<int>((size_t)nv_out), *d_order = T.get<int>((size_t)nv_out), *d_rank = T.get<int>((size_t)nv_out);
-        if (!d_ov || !d_of || !d_key || !d_key2 || !d_idx || !d_order || !d_rank) RM_RETURN(NW_ERR_NOMEM);
-        {
-            // Morton order of the result's vertices (see k_rm_vertex_keys); the bounding cube is the input's
-            double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-            for (int64_t v = 0; v < nv_in; ++v) for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], (double)vertices[3 * v + k]); hi[k] = std::max(hi[k], (double)vertices[3 * v + k]); }
-            const double ext = std::max({hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2], 1e-30});
-            hipLaunchKernelGGL(k_rm_vertex_keys, RM_GRID(nv), 0, st, m, nv, d_used, d_vert_at, lo[0], lo[1], lo[2], 1024.0 / ext, d_key, d_idx);
-            size_t sort_bytes = 0;
-            if (hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, d_key, d_key2, d_idx, d_order, nv_out, 0, 30, st) != hipSuccess) RM_RETURN(NW_ERR_HIP);
-            void *d_sort = T.get<unsigned char>(sort_bytes + 16);
-            if (!d_sort) RM_RETURN(NW_ERR_NOMEM);
-            if (hipcub::DeviceRadixSort::SortPairs(d_sort, sort_bytes, d_key, d_key2, d_idx, d_order, nv_out, 0, 30, st) != hipSuccess) RM_RETURN(NW_ERR_HIP);
-            hipLaunchKernelGGL(k_rm_rank, RM_GRID(nv_out), 0, st, d_order, nv_out, d_rank);
-        }
+        float *d_ov = temp.get<float>(3 * (size_t)nv_out); int *d_of = temp.get<int>(3 * (size_t)nf_out);
+        unsigned *d_key = temp.get<unsigned>((size_t)nv_out), *d_key2 = temp.get<unsigned>((size_t)nv_out);
+        int *d_idx = temp.get<int>((size_t)nv_out), *d_order = temp.get<int>((size_t)nv_out), *d_rank = temp.get<int>((size_t)nv_out);
+        if (!d_ov || !d_of || !d_key || !d_key2 || !d_idx || !d_order || !d_rank) return NW_ERR_NOMEM;
+        // Morton order of the result's vertices (see k_rm_vertex_keys); the bounding cube is the input's
+        hipLaunchKernelGGL(k_rm_vertex_keys, RM_GRID(nv), 0, st, m, nv, d_used, d_vert_at, in.cube.lo[0], in.cube.lo[1], in.cube.lo[2], in.cube.per_unit, d_key, d_idx);
+        size_t sort_bytes = 0;
+        if (hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, d_key, d_key2, d_idx, d_order, nv_out, 0, 30, st) != hipSuccess) return NW_ERR_HIP;
+        void *d_sort = temp.get<unsigned char>(sort_bytes + 16);
+        if (!d_sort) return NW_ERR_NOMEM;
+        if (hipcub::DeviceRadixSort::SortPairs(d_sort, sort_bytes, d_key, d_key2, d_idx, d_order, nv_out, 0, 30, st) != hipSuccess) return NW_ERR_HIP;
+        hipLaunchKernelGGL(k_rm_rank, RM_GRID(nv_out), 0, st, d_order, nv_out, d_rank);
         hipLaunchKernelGGL(k_rm_write_out, dim3(nblk), dim3(256), 0, st, m, nv, nf, d_alive, d_face_at, d_used, d_vert_at, d_rank, d_ov, d_of, d_part);
-        ov.resize(3 * (size_t)nv_out);
-        of.resize(3 * (size_t)nf_out);
-        std::vector<double> lens((size_t)nblk);
-        int c[RC_COUNT];
-        RM_HIP(hipMemcpyAsync(ov.data(), d_ov, sizeof(float) * ov.size(), hipMemcpyDeviceToHost, st));
-        RM_HIP(hipMemcpyAsync(of.data(), d_of, sizeof(int) * of.size(), hipMemcpyDeviceToHost, st));
-        RM_HIP(hipMemcpyAsync(lens.data(), d_part, sizeof(double) * (size_t)nblk, hipMemcpyDeviceToHost, st));
-        RM_HIP(hipMemcpyAsync(c, d_cnt, sizeof(c), hipMemcpyDeviceToHost, st));
-        RM_HIP(hipStreamSynchronize(st));
+        sums.resize((size_t)nblk);
+        out->v = (float *)std::malloc(sizeof(float) * std::max<size_t>(3 * (size_t)nv_out, 3));
+        out->f = (int32_t *)std::malloc(sizeof(int32_t) * std::max<size_t>(3 * (size_t)nf_out, 3));
+        if (!out->v || !out->f) return NW_ERR_NOMEM;
+        out->nv = nv_out; out->nf = nf_out;
+        RM_HIP(hipMemcpyAsync(out->v, d_ov, sizeof(float) * 3 * (size_t)nv_out, hipMemcpyDeviceToHost, st));
+        RM_HIP(hipMemcpyAsync(out->f, d_of, sizeof(int) * 3 * (size_t)nf_out, hipMemcpyDeviceToHost, st));
+        RM_HIP(hipMemcpyAsync(sums.data(), d_part, sizeof(double) * (size_t)nblk, hipMemcpyDeviceToHost, st));
+        RM_TRY(read_counters());
         if (stats) {
             double s = 0.0;
-            for (double l : lens) s += l;
-            stats->n_split = c[RC_SPLIT]; stats->n_collapse = c[RC_COLLAPSE]; stats->n_flip = c[RC_FLIP];
+            for (double l : sums) s += l;
+            stats->n_split = cnt[RC_SPLIT]; stats->n_collapse = cnt[RC_COLLAPSE]; stats->n_flip = cnt[RC_FLIP];
             stats->mean_edge_length = nf_out ? s / (3.0 * nf_out) : 0.0;
-            stats->max_valence = c[RC_MAXVAL];
+            stats->max_valence = cnt[RC_MAXVAL];
             stats->rounds_split = rounds[0]; stats->rounds_collapse = rounds[1]; stats->rounds_flip = rounds[2];
         }
-        if (verbose) std::fprintf(stderr, "[nw_remesh_device] set-up %.2f ms, passes %.2f ms (%d + %d + %d rounds), result %.2f ms\n", ms(t0, t1), ms(t1, t2), rounds[0], rounds[1],
-                                  rounds[2], ms(t2, now()));
+        return NW_OK;
     }
-    return NW_OK;
-}
+
+    // the phases in order -> NW_OK, RM_RETRY or an error.  A phase that fails just returns: here, in one place, the stream is drained behind it
+    // (asynchronous copies into this Attempt's members or the arrays of `out` may be in flight; both outlive this call)
+    int run(double room, Output *out, nw_remesh_stats *stats)
+    {
+        int rc = measure(room);
+        if (rc == NW_OK) rc = load();
+        bool last = false;
+        for (int it = 0; rc == NW_OK && it < in.n_iterations && !last; ++it) rc = iteration(it, &last);
+        t2 = now();
+        if (rc == NW_OK) rc = result(out, stats);
+        if (rc != NW_OK) (void)hipStreamSynchronize(st);
+        else if (in.verbose) std::fprintf(stderr, "[nw_remesh_device] set-up %.2f ms, passes %.2f ms (%d + %d + %d rounds), result %.2f ms\n", ms(t0, t1), ms(t1, t2), rounds[0], rounds[1],
+                                          rounds[2], ms(t2, now()));
+        return rc;
+    }
+};
 
 }  // namespace
 
@@ -954,31 +965,25 @@ NW_EXPORT int nw_remesh_device(int device, const float *vertices, int64_t n_vert
         if (hipHostMalloc((void **)&g_session.h_cand, sizeof(int) * ROUNDS_CAP, hipHostMallocDefault) != hipSuccess) { (void)hipStreamDestroy(g_session.stream); g_session = Session(); return NW_ERR_NOMEM; }
         g_session.device = device;
     }
-    const bool verbose = std::getenv("NWR_VERBOSE") != nullptr;
-    const int mv = max_valence > 0 ? std::min(max_valence, 60) : 16;
+    const char *verbose = std::getenv("NWR_VERBOSE");
     try {
-        std::vector<float> ov;
-        std::vector<int32_t> of;
+        const Input in{vertices, n_vertices, faces, n_faces, n_iterations, (double)target_edge_length, (double)relax_lambda, n_relax, rm_plan::effective_max_valence(max_valence),
+                       rm_plan::morton_cube(vertices, n_vertices), verbose ? (std::atoi(verbose) >= 2 ? 2 : 1) : 0};
+        Output out;
         int rc = RM_RETRY;
-        double room = 1.5;
-        if (const char *e = std::getenv("NW_REMESH_ROOM")) room = std::max(0.05, std::atof(e));      // (tests: start too small, so that the retry runs)
+        double room = rm_plan::first_room(std::getenv("NW_REMESH_ROOM"));
         // (slots of faces and vertices that die are not used again within a call: a target far below the input's lengths, where the split pass
         // overshoots and the collapses take a third back, needs several times the final size -- the attempt that runs out stops at once)
-        for (int tries = 0; tries < 8 && rc == RM_RETRY; ++tries, room *= 2.0) {
-            rc = attempt(vertices, n_vertices, faces, n_faces, n_iterations, (double)target_edge_length, (double)relax_lambda, n_relax, mv, room, ov, of, stats, verbose);
-            if (rc == RM_RETRY && verbose) std::fprintf(stderr, "[nw_remesh_device] out of room at %.1f x the expected faces: again with twice that\n", room);
+        for (int tries = 0; tries < rm_plan::TRIES && rc == RM_RETRY; ++tries, room = rm_plan::next_room(room)) {
+            rc = Attempt(in).run(room, &out, stats);
+            if (rc == RM_RETRY && in.verbose) std::fprintf(stderr, "[nw_remesh_device] out of room at %.1f x the expected faces: again with twice that\n", room);
         }
-        if (rc == RM_RETRY) return NW_ERR_NOMEM;
-        if (rc != NW_OK) return rc;
-        float *pv = (float *)std::malloc(sizeof(float) * std::max<size_t>(ov.size(), 3));
-        int32_t *pf = (int32_t *)std::malloc(sizeof(int32_t) * std::max<size_t>(of.size(), 3));
-        if (!pv || !pf) { std::free(pv); std::free(pf); return NW_ERR_NOMEM; }
-        std::memcpy(pv, ov.data(), sizeof(float) * ov.size());
-        std::memcpy(pf, of.data(), sizeof(int32_t) * of.size());
-        *out_vertices = pv; *out_n_vertices = (int64_t)(ov.size() / 3); *out_faces = pf; *out_n_faces = (int64_t)(of.size() / 3);
+        if (rc != NW_OK) return rc == RM_RETRY ? NW_ERR_NOMEM : rc;
+        *out_vertices = out.v; *out_n_vertices = out.nv; *out_faces = out.f; *out_n_faces = out.nf;
+        out.v = nullptr; out.f = nullptr;                   // (the caller's from here on: nw_host_free)
         return NW_OK;
     } catch (const std::exception &) {
-        (void)hipStreamSynchronize(g_session.stream);       // (as RM_RETURN: nothing of the call may still be in flight)
+        (void)hipStreamSynchronize(g_session.stream);       // (as Attempt::run: nothing of the call may still be in flight)
         return NW_ERR_NOMEM;
     }
 }

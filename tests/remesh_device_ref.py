@@ -29,6 +29,22 @@ R_MAX = (24, 32, 24)          # rounds of a split / collapse / flip pass at most
 _M32 = 0xffffffff
 
 
+def pass_goes_on(bids_of, r):
+    """is round r of a pass run?  bids_of: the bidders of its rounds 0 .. r-1.  Not after a round without a bidder, and not after a round, the
+    last one aside, with so few that the next iteration may as well have them"""
+    return not (any(b == 0 for b in bids_of) or any(0 < b < 8 and 500 * b < bids_of[0] for b in bids_of[:max(r - 1, 0)]))
+
+
+def sweeps_end(n_list, first_list):
+    """a split sweep over a handful of edges is left to the next iteration"""
+    return n_list < 32 and n_list * 200 < first_list
+
+
+def iterations_end(n_relax, before, now):
+    """before, now: (splits, collapses, flips) so far; an iteration that changed nothing would be repeated unchanged by every later one"""
+    return n_relax == 0 and tuple(before) == tuple(now)
+
+
 class Refused(ValueError):
     """what the device refuses: .code is 'bad argument' or 'non-manifold'"""
     def __init__(self, code, why):
@@ -574,7 +590,7 @@ class _Mesh:
         self.passes[kind] += 1
         bids_of = []
         for r in range(R_MAX[kind]):
-            if any(b == 0 for b in bids_of) or any(0 < b < 8 and 500 * b < bids_of[0] for b in bids_of[:max(r - 1, 0)]):
+            if not pass_goes_on(bids_of, r):
                 break
             self.seed = (self.pass_seq * 64 + r) & _M32
             self.rounds[kind] += 1
@@ -679,13 +695,13 @@ def remesh_device_ref(v, f, n, L, l=0.5, n_relax=0, max_valence=16, check=True):
                 break
             if sweep == 0:
                 first_list = n_list
-            if n_list < 32 and n_list * 200 < first_list:
+            if sweeps_end(n_list, first_list):
                 break
         m.run_pass(1)
         m.run_pass(2)
         for _k in range(int(n_relax)):
             m.relax(l)
-        if n_relax == 0 and before == (m.n_split, m.n_collapse, m.n_flip):
+        if iterations_end(n_relax, before, (m.n_split, m.n_collapse, m.n_flip)):
             break
     ov, of, mean, mv = m.result()
     info = dict(n_split=m.n_split, n_collapse=m.n_collapse, n_flip=m.n_flip, rounds=tuple(m.rounds), passes=tuple(m.passes), max_valence=mv,
