@@ -37,6 +37,7 @@ OBJ_ISOSURFACE = _csrc('nw_isosurface.o')
 OBJ_EVALUATION = _csrc('nw_evaluation.o')
 OBJ_SIMULATION = _csrc('nw_simulation.o')
 OBJ_DISTANCE = _csrc('nw_distance.o')
+OBJ_NEIGHBOURS = _csrc('nw_neighbours.o')
 # the translation units of libnanowrap_hip.so: (source, object, what else it is rebuilt for, flags).  The objects are linked in this order.
 UNITS = [
     # the per-iteration kernels and the C-ABI; every header of csrc/ but nw_bq.h and nw_bq_core.h is included by it (directly or through
@@ -63,7 +64,10 @@ UNITS = [
     # the exact signed distance from points to the mesh (nw_distance_core.h: the point-triangle distance and the pseudonormals, which the
     # tests also compile for the CPU)
     (_csrc('nw_distance.hip'), OBJ_DISTANCE, [_include('nw_distance.h'), _csrc('nw_distance_core.h')] + _BQ_H, _QUERY),
-    # what the six above share (csrc/nw_bq.h): the exclusive scan and the point grid's bounding box and counting sort, float and double
+    # the exact k-th-nearest-neighbour distance, for query lists and for the nodes of a voxel lattice (nw_neighbours_core.h: the list of
+    # the k best, the ring bound and the quantisation, which the tests also compile for the CPU)
+    (_csrc('nw_neighbours.hip'), OBJ_NEIGHBOURS, [_include('nw_neighbours.h'), _csrc('nw_neighbours_core.h')] + _BQ_H, _QUERY),
+    # what the seven above share (csrc/nw_bq.h): the exclusive scan and the point grid's bounding box and counting sort, float and double
     (_csrc('nw_bq.hip'), OBJ_BQ, _BQ, _QUERY),
 ]
 DEPS = sorted(set(d for src, _, extra, _ in UNITS for d in [src] + extra))
@@ -168,7 +172,11 @@ KERNEL_BUDGETS = {
     'k_md_rho_reduce':                (24, 64),            # LDS = the four waves' maxima and sums
     'k_md_query':                     (128, 64),           # float64 query, best record (d2, d, closest point, face, feature) and one exact test in flight: 4 waves per SIMD; LDS = the four waves' sums
     'k_md_sum_final':                 (16, 64),
-    # what the six units above share (csrc/nw_bq.o): the exclusive scan, and the point grid of hole punching (f32) and of the metric (f64)
+    # the k-th-neighbour distance (csrc/nw_neighbours.o): set-up queries in float64, budgeted for zero scratch (a lane's k best live in LDS,
+    # never in a register array indexed at run time) and against silent growth
+    'k_kn_queries':                   (64, 32 * 1024),     # LDS = 128 lanes x 32 slots x 8 bytes
+    'k_kn_nodes':                     (64, 32 * 1024),
+    # what the seven units above share (csrc/nw_bq.o): the exclusive scan, and the point grid of hole punching (f32) and of the metric (f64)
     'k_bq_scan_tiles':                (32, 1024),
     'k_bq_scan_bsums':                (32, 1024),
     'k_bq_scan_final':                (32, 1024),
@@ -179,7 +187,7 @@ KERNEL_BUDGETS = {
     'k_bq_cell_count_f64':            (48, 0),
     'k_bq_scatter_f64':               (16, 0),
 }
-BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_DISTANCE, OBJ_BQ]
+BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_DISTANCE, OBJ_NEIGHBOURS, OBJ_BQ]
 
 
 def kernel_resources(obj=None):

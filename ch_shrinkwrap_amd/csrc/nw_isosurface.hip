@@ -270,6 +270,7 @@ struct nwi_ctx : bq::Ctx {
     nwi_grid grid{};
     int n_vox = 0, passes = 0;
     int64_t n_points = 0;
+    bool have_counts = false;       // the field came from nwi_density: nwi_threshold_auto has counts to select over
     DevBuf counts, field_a, field_b, pts;
     u64 *field = nullptr;
     // the sheet table
@@ -356,6 +357,7 @@ NWI_EXPORT int nwi_density(nwi_ctx *ctx, const float *xyz, int64_t n_points, int
     NWI_HIP(hipSetDevice(ctx->device));
     const int n = (int)n_points, nv = (int)nvox;
     ctx->n_vox = 0;
+    ctx->have_counts = false;
     ctx->n_vertices = ctx->n_faces = -1;
     const float *src = xyz;
     if (!points_on_device) {
@@ -392,6 +394,35 @@ NWI_EXPORT int nwi_density(nwi_ctx *ctx, const float *xyz, int64_t n_points, int
     ctx->passes = passes;
     ctx->n_points = n_points;
     ctx->n_vox = nv;
+    ctx->have_counts = true;
+    return NWI_OK;
+}
+
+NWI_EXPORT int nwi_set_field(nwi_ctx *ctx, const uint64_t *field, int on_device, const float *lo, float h, const int32_t *dims)
+{
+    if (!field || !lo || !dims || (on_device != 0 && on_device != 1) || !(h > 0.0f) || !std::isfinite(h)) return NWI_ERR_BADARG;
+    int64_t nvox = 1;
+    for (int d = 0; d < 3; ++d) {
+        if (!std::isfinite(lo[d]) || dims[d] < 3 || dims[d] > NWI_MAX_DIM) return NWI_ERR_BADARG;
+        nvox *= dims[d];
+    }
+    if (nvox > (1ll << 30)) return NWI_ERR_BADARG;
+    if (!ctx) return NWI_ERR_BADARG;
+    NWI_HIP(hipSetDevice(ctx->device));
+    ctx->n_vox = 0;
+    ctx->have_counts = false;
+    ctx->n_vertices = ctx->n_faces = -1;
+    NWI_HIP(ctx->field_a.ensure(sizeof(u64) * (size_t)nvox));
+    NWI_HIP(ctx->small.ensure(sizeof(unsigned) * 512));         // (nwi_extract's flag word lives there)
+    NWI_HIP(hipMemcpyAsync(ctx->field_a.p, field, sizeof(u64) * (size_t)nvox, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    NWI_HIP(hipStreamSynchronize(ctx->stream));                 // (the caller's field is not read after the call)
+    for (int d = 0; d < 3; ++d) { ctx->grid.lo[d] = lo[d]; ctx->grid.dims[d] = dims[d]; }
+    ctx->grid.h = h;
+    ctx->grid.inv_h = 1.0f / h;
+    ctx->field = ctx->field_a.as<u64>();
+    ctx->passes = 0;
+    ctx->n_points = 0;
+    ctx->n_vox = (int)nvox;
     return NWI_OK;
 }
 
@@ -399,7 +430,7 @@ NWI_EXPORT int nwi_threshold_auto(nwi_ctx *ctx, double fraction, uint64_t *media
 {
     if (!thr || !(fraction >= 0.0) || !std::isfinite(fraction)) return NWI_ERR_BADARG;
     if (!ctx) return NWI_ERR_BADARG;
-    if (ctx->n_vox < 1) return fail(ctx, NWI_ERR_STATE, "nwi_threshold_auto: nwi_density first");
+    if (ctx->n_vox < 1 || !ctx->have_counts) return fail(ctx, NWI_ERR_STATE, "nwi_threshold_auto: nwi_density first");
     NWI_HIP(hipSetDevice(ctx->device));
     // no field value exceeds n_points * 4^(3 passes): the bytes above it are zero and need no pass
     const u64 vmax = (u64)ctx->n_points << (6 * ctx->passes);

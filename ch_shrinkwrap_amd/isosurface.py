@@ -11,6 +11,8 @@ to the local number of points, and one resolution for the whole surface.  `thres
 per nm^3).
 
     density_isosurface   cloud -> (vertices, faces, info): the raw isosurface, outer and inner sheets alike
+    knn_isosurface       the same from the k-NN density (neighbours.py): the bandwidth follows (threshold_density, n_points_min) or the
+                         cloud's own density, and the voxel size is resolution only
     start_surface        ... then the inner sheets and dust dropped (surgery.inner_components) and the mesh remeshed (remesh_device)
     DensitySurface       the recipe-module mirror: DensitySurface().execute(ns); ShrinkwrapMembrane().execute(ns)
 
@@ -24,7 +26,7 @@ import numpy as np
 from . import _lib
 
 SYMBOLS = ['nwi_abi_version', 'nwi_create', 'nwi_destroy', 'nwi_last_error', 'nwi_set_sheet_table', 'nwi_density', 'nwi_threshold_auto',
-           'nwi_extract', 'nwi_get']
+           'nwi_extract', 'nwi_get', 'nwi_set_field']
 ABI_VERSION = 1
 MAX_PASSES = 5
 (NWI_OK, NWI_ERR_BADARG, NWI_ERR_HIP, NWI_ERR_NONFINITE, NWI_ERR_NOMEM, NWI_ERR_OUTSIDE, NWI_ERR_STATE, NWI_ERR_BORDER,
@@ -47,7 +49,8 @@ def load():
             'nwi_density': [vp, vp, i64, i32, vp, f32, vp, i32, vp, vp],
             'nwi_threshold_auto': [vp, f64, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(f64), ctypes.POINTER(i64)],
             'nwi_extract': [vp, u64, ctypes.POINTER(i64), ctypes.POINTER(i64)],
-            'nwi_get': [vp, vp, vp, vp]}, 'nwi_abi_version', ABI_VERSION, 'nw_isosurface')
+            'nwi_get': [vp, vp, vp, vp],
+            'nwi_set_field': [vp, vp, i32, vp, f32, vp]}, 'nwi_abi_version', ABI_VERSION, 'nw_isosurface')
     return _L
 
 
@@ -123,6 +126,20 @@ class IsosurfaceContext(_lib.QueryContext):
         self.dims, self.h_voxel, self.passes = dims, float(np.float32(h)), int(passes)
         return (field, counts) if return_field and return_counts else field if return_field else counts
 
+    def set_field(self, field, lo, h, dims):
+        """Adopt a field made elsewhere, by copy: a uint64 host array [z, y, x], or a raw device pointer (an int) to dims[2] x dims[1] x
+        dims[0] values.  extract works on it; threshold_auto does not (there are no counts) until the next density."""
+        lo = np.ascontiguousarray(lo, np.float32).reshape(3)
+        dims = np.ascontiguousarray(dims, np.int32).reshape(3)
+        if isinstance(field, (int, np.integer)):
+            src, on_device = int(field), 1
+        else:
+            src, on_device = np.ascontiguousarray(field, np.uint64), 0
+            if src.shape != (int(dims[2]), int(dims[1]), int(dims[0])):
+                raise ValueError('set_field: the field must be indexed [z, y, x] with the shape of dims')
+        self.check(self.L.nwi_set_field(self.h, _p(src), on_device, _p(lo), float(h), _p(dims)), 'nwi_set_field')
+        self.dims, self.h_voxel, self.passes = dims, float(np.float32(h)), 0
+
     def threshold_auto(self, fraction=0.3):
         """dict(median, thr (field values), threshold_density (nm^-3), n_occupied): thr = floor(fraction * lower median of the field over
         the occupied voxels)."""
@@ -181,6 +198,61 @@ def density_isosurface(points, voxel_size=None, passes=2, threshold_density=None
     return v, f, info
 
 
+def knn_threshold(h, n_points_min, threshold_density):
+    """(R_thr, r_cap, pad, thr) of the level set of the k-NN density k / (4/3 pi r_k^3) at threshold_density on a lattice of spacing h:
+    R_thr = (3 k / (4 pi threshold_density))^(1/3) is where r_k crosses; r_cap = R_thr + 2 h is where the field is clamped (r_k is
+    1-Lipschitz, so the outer node of every crossed lattice edge lies below the cap and is not clamped); pad = ceil(R_thr / h) + 2
+    voxels of margin keep every border node more than R_thr from the cloud, hence outside; thr = floor((r_cap - R_thr) 2^20) is the
+    level in the field's units."""
+    k, td, h = int(n_points_min), float(threshold_density), float(h)
+    if not (td > 0 and np.isfinite(td)):
+        raise ValueError('knn_isosurface: threshold_density must be positive and finite (is the cloud k + 1 coincident points?)')
+    R_thr = float(np.cbrt(3.0 * k / (4.0 * np.pi * td)))
+    r_cap = R_thr + 2.0 * h
+    return R_thr, r_cap, int(np.ceil(R_thr / h)) + 2, int(np.floor((r_cap - R_thr) * float(1 << 20)))
+
+
+def knn_isosurface(points, voxel_size=None, n_points_min=20, threshold_density=None, threshold_fraction=0.3, device=0, sigma=None):
+    """(vertices float32, faces int32, info) of the isosurface of the k-NN density of the cloud, k = n_points_min (upstream's
+    Octree.n_points_min): the level set r_k(x) = R_thr of the distance to the k-th nearest localization, which is where a ball of
+    radius R_thr holds k localizations.  The bandwidth R_thr follows (threshold_density, n_points_min) and not the voxel size, which is
+    resolution only.  threshold_density (nm^-3, upstream's DualMarchingCubes.threshold_density) None: threshold_fraction x the median
+    of neighbours.local_density(points, n_points_min), so that R_thr follows the cloud.  voxel_size None: pick_voxel_size(points, sigma).
+    Still not PYME's octree: a regular grid at one resolution.  The field (neighbours.NeighbourContext.node_field) goes from its kernel
+    to the surface nets on the device; it never visits the host.  As with density_isosurface the surface has an inner sheet wherever
+    the cloud is a shell."""
+    from . import neighbours
+    pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    k = int(n_points_min)
+    if not 1 <= k < neighbours.MAX_K:
+        raise ValueError('n_points_min must be in 1..%d' % (neighbours.MAX_K - 1))
+    h = float(np.float32(pick_voxel_size(pts, sigma) if voxel_size is None else voxel_size))
+    nctx = neighbours.NeighbourContext(device)
+    try:
+        t0 = time.time()
+        median = None
+        if threshold_density is None:
+            median = float(np.median(neighbours.local_density(pts, k, context=nctx)))
+            threshold_density = float(threshold_fraction) * median
+        else:
+            nctx.set_cloud(pts)
+        R_thr, r_cap, pad, thr = knn_threshold(h, k, threshold_density)
+        lo, dims = grid_for(pts, h, pad)
+        nctx.node_field(lo, h, dims, k, r_cap)
+        ctx = IsosurfaceContext(device)
+        try:
+            ctx.set_field(nctx.field_pointer(), lo, h, dims)
+            v, f = ctx.extract(thr)
+        finally:
+            ctx.close()
+        dt = time.time() - t0
+    finally:
+        nctx.close()
+    info = dict(lo=lo, h=h, dims=dims, pad=pad, thr=thr, n_points_min=k, R_thr=R_thr, r_cap=r_cap, threshold_density=float(threshold_density),
+                median_density=median, seconds=dt)
+    return v, f, info
+
+
 class Surface(object):
     """What start_surface returns: anything with .vertices / .faces is a start surface for ShrinkwrapMembrane."""
 
@@ -195,13 +267,20 @@ def mean_edge_length(vertices, faces):
 
 
 def start_surface(points, voxel_size=None, passes=2, threshold_density=None, threshold_fraction=0.3, pad=None, device=0, sigma=None,
-                  cull_inner=True, remesh=True, target_edge_length=None, min_component_faces=32):
-    """density_isosurface, then the package's existing pieces: components by SurgeryContext.label_faces / component_stats, inner sheets by
+                  cull_inner=True, remesh=True, target_edge_length=None, min_component_faces=32, method='grid', n_points_min=20):
+    """density_isosurface (method='grid') or knn_isosurface (method='knn', with n_points_min; passes and pad do not apply), then the
+    package's existing pieces: components by SurgeryContext.label_faces / component_stats, inner sheets by
     surgery.inner_components (inverted shells, shells inside a kept one), dust below min_component_faces faces, and three passes of
     remesh_device at target_edge_length (default: the mesh's own mean edge length, as the synthetic start meshes are made).
     Returns a Surface (.vertices, .faces, .info)."""
     from . import surgery
-    v, f, info = density_isosurface(points, voxel_size, passes, threshold_density, threshold_fraction, pad, device, sigma)
+    if method == 'grid':
+        v, f, info = density_isosurface(points, voxel_size, passes, threshold_density, threshold_fraction, pad, device, sigma)
+    elif method == 'knn':
+        v, f, info = knn_isosurface(points, voxel_size, n_points_min, threshold_density, threshold_fraction, device, sigma)
+    else:
+        raise ValueError("start_surface: method must be 'grid' or 'knn'")
+    info['method'] = method
     t0 = time.time()
     ctx = surgery.SurgeryContext(device)
     try:
@@ -248,6 +327,8 @@ class DensitySurface(object):
         self.remesh = True                         # DualMarchingCubes.remesh
         self.voxel_size = None                     # nm; None = the median of the `sigma_x` column, or pick_voxel_size's rule without one
         self.passes = 2
+        self.method = 'grid'                       # 'knn': the level set of the k-NN density (knn_isosurface), bandwidth from n_points_min and the threshold
+        self.n_points_min = 20                     # Octree.n_points_min: the k of method = 'knn'
         self.cull_inner_surfaces = True
         self.min_component_faces = 32
         self.target_edge_length = None
@@ -267,6 +348,7 @@ class DensitySurface(object):
             sigma = None
         surf = start_surface(pts, voxel_size=self.voxel_size, passes=self.passes, threshold_density=self.threshold_density,
                              threshold_fraction=self.threshold_fraction, device=self.device, sigma=sigma, cull_inner=self.cull_inner_surfaces,
-                             remesh=self.remesh, target_edge_length=self.target_edge_length, min_component_faces=self.min_component_faces)
+                             remesh=self.remesh, target_edge_length=self.target_edge_length, min_component_faces=self.min_component_faces,
+                             method=self.method, n_points_min=self.n_points_min)
         namespace[self.output] = surf
         return surf

@@ -1,9 +1,10 @@
 """
 The reference's evaluation recipe (ch_shrinkwrap/test_evaluation_recipe.yaml in the reference) end to end, every stage on the GPU:
 
-    python examples/evaluate_shape.py [shape] [p]
+    python examples/evaluate_shape.py [shape] [p] [knn]
         (shape: a name of ch_shrinkwrap_amd.simulation.SHAPES with the parameters below, default TwoToruses; p: the share of the
-        fluorophores that is detected, default 0.1)
+        fluorophores that is detected, default 0.1; a trailing `knn` makes the start surface the level set of the k-NN density,
+        DensitySurface(method='knn'), which is what lets p go down towards upstream's sweep)
 
     PointcloudFromShape (the noisy cloud) and PointcloudFromShape (the raw truth cloud: density 0.008, p = 1, no_jitter)
       -> DensitySurface (in the place of upstream's Octree -> DualMarchingCubes) -> ShrinkwrapMembrane(max_iters=29, neck_first_iter=0)
@@ -25,7 +26,7 @@ PARAMS = {'TwoToruses': "{'r': 30, 'R': 100}", 'Sphere': "{'radius': 100}", 'Dua
           'NToruses': "{'toruses': {'one': {'r': 30, 'R': 100}, 'two': {'r': 10, 'R': 75}, 'three': {'r': 30, 'R': 150}}}"}
 
 
-def main(shape='TwoToruses', p=0.1, seed=0):
+def main(shape='TwoToruses', p=0.1, seed=0, method='grid'):
     if shape not in PARAMS:
         raise SystemExit('shape is one of %s' % ', '.join(sorted(PARAMS)))
     ns = {}
@@ -35,7 +36,7 @@ def main(shape='TwoToruses', p=0.1, seed=0):
     raw = PointcloudFromShape(output='raw', shape_name=shape, shape_params=PARAMS[shape], density=0.008, p=1.0, no_jitter=True, seed=seed).execute(ns)
     t_sim = time.time() - t0
     print('%s: %d localizations, %d truth points in %.2f s' % (shape, cloud['x'].size, raw['x'].size, t_sim))
-    surf = DensitySurface().execute(ns)
+    surf = DensitySurface(method=method).execute(ns)
     print('start surface: %d vertices / %d faces' % (surf.vertices.shape[0], surf.faces.shape[0]))
     t0 = time.time()
     mesh = ShrinkwrapMembrane(max_iters=29, neck_first_iter=0).execute(ns)
@@ -47,4 +48,7 @@ def main(shape='TwoToruses', p=0.1, seed=0):
 
 
 if __name__ == '__main__':
-    main(sys.argv[1] if len(sys.argv) > 1 else 'TwoToruses', float(sys.argv[2]) if len(sys.argv) > 2 else 0.1)
+    args = sys.argv[1:]
+    method = 'knn' if args and args[-1] == 'knn' else 'grid'
+    args = args[:-1] if method == 'knn' else args
+    main(args[0] if len(args) > 0 else 'TwoToruses', float(args[1]) if len(args) > 1 else 0.1, method=method)

@@ -1,9 +1,10 @@
 """
 End-to-end example from the localizations alone: the start surface is made from the cloud, not handed in.
 
-    python examples/fit_from_cloud.py [scale] [host | device]
+    python examples/fit_from_cloud.py [scale] [host | device] [knn]
         (scale 0.1 = 500 000 localizations, default; 1.0 = 5 000 000; the second argument is where the fit is scored:
-        evaluation.fit_quality's backend, default host)
+        evaluation.fit_quality's backend, default host; a trailing `knn` makes the start surface the level set of the k-NN density,
+        DensitySurface(method='knn'), whose bandwidth follows the cloud instead of the voxel size)
 
 Upstream's recipe (ch_shrinkwrap/test_evaluation_recipe.yaml:25-38 in the reference) is Octree -> DualMarchingCubes -> ShrinkwrapMembrane;
 here `DensitySurface` stands in for the first two (a regular-grid density isosurface on the GPU: it is not PYME's algorithm, see
@@ -22,7 +23,7 @@ from ch_shrinkwrap_amd.membrane_mesh import ShrinkwrapMembrane     # noqa: E402
 from ch_shrinkwrap_amd.surgery import euler_characteristic        # noqa: E402
 
 
-def main(scale=0.1, score_backend='host'):
+def main(scale=0.1, score_backend='host', method='grid'):
     cfg = synth.make_config('c4', scale=scale, seed=0)
     pts = cfg['points']
     table = {'x': pts[:, 0], 'y': pts[:, 1], 'z': pts[:, 2],
@@ -31,7 +32,7 @@ def main(scale=0.1, score_backend='host'):
     # a sparser cloud needs a coarser grid: 8 nm at full size, 12 nm below (the sizes profiles/isosurface_c4.txt and the tests use)
     voxel = 8.0 if scale >= 1.0 else 12.0
     t0 = time.time()
-    surf = DensitySurface(voxel_size=voxel).execute(ns)
+    surf = DensitySurface(voxel_size=voxel, method=method).execute(ns)
     t_surf = time.time() - t0
     chi = euler_characteristic(surf.faces)
     print('%d localizations -> start surface of %d vertices / %d faces in %.2f s (voxel %.1f nm, %d components found, %d removed), genus %d'
@@ -47,4 +48,7 @@ def main(scale=0.1, score_backend='host'):
 
 
 if __name__ == '__main__':
-    main(float(sys.argv[1]) if len(sys.argv) > 1 else 0.1, sys.argv[2] if len(sys.argv) > 2 else 'host')
+    args = sys.argv[1:]
+    method = 'knn' if args and args[-1] == 'knn' else 'grid'
+    args = args[:-1] if method == 'knn' else args
+    main(float(args[0]) if len(args) > 0 else 0.1, args[1] if len(args) > 1 else 'host', method)

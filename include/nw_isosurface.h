@@ -57,7 +57,7 @@ typedef enum nwi_status {
     NWI_ERR_NONFINITE = -3,   /* a non-finite localization */
     NWI_ERR_NOMEM = -4,
     NWI_ERR_OUTSIDE = -5,     /* a localization outside the grid (nothing is dropped silently) */
-    NWI_ERR_STATE = -6,       /* a call before the one it needs: nwi_density, nwi_set_sheet_table, nwi_extract */
+    NWI_ERR_STATE = -6,       /* a call before the one it needs: nwi_density (or nwi_set_field), nwi_set_sheet_table, nwi_extract */
     NWI_ERR_BORDER = -7,      /* an inside node on the outermost layer of the grid: pad the grid */
     NWI_ERR_EMPTY = -8        /* no occupied voxel (nwi_threshold_auto) or no node pair across the threshold (nwi_extract) */
 } nwi_status;
@@ -76,6 +76,12 @@ int nwi_set_sheet_table(nwi_ctx *ctx, const int8_t *table);
  * field_out (may be NULL): dims[2] x dims[1] x dims[0] uint64, x fastest; counts_out (may be NULL): the same shape in uint32. */
 int nwi_density(nwi_ctx *ctx, const float *xyz, int64_t n_points, int points_on_device, const float *lo, float h, const int32_t *dims,
                 int passes, uint64_t *field_out, uint32_t *counts_out);
+
+/* Adopts a field made elsewhere (nwk_node_field of include/nw_neighbours.h, or a host array) by copy: dims[2] x dims[1] x dims[0] uint64,
+ * x fastest, a host pointer (on_device = 0) or a device pointer (1: complete before the call, not read after it); lo, h and dims as
+ * nwi_density takes them, with the same limits.  Afterwards the context is in the state nwi_extract needs; there are no counts, so
+ * nwi_threshold_auto returns NWI_ERR_STATE until the next nwi_density. */
+int nwi_set_field(nwi_ctx *ctx, const uint64_t *field, int on_device, const float *lo, float h, const int32_t *dims);
 
 /* median, threshold (both field values), threshold as a density in nm^-3, number of occupied voxels; each output may be NULL but thr. */
 int nwi_threshold_auto(nwi_ctx *ctx, double fraction, uint64_t *median, uint64_t *thr, double *density, int64_t *n_occupied);
