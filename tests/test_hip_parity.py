@@ -283,7 +283,7 @@ def test_full_size_properties(name, n_brute):
     x = rng.normal(size=3 * cg.M).astype('f4')
     y = rng.normal(size=3 * cg.M).astype('f4')
     assert np.allclose(cg.Afunc(x + 2 * y), cg.Afunc(x) + 2 * cg.Afunc(y), atol=1e-4)
-    # (4) the step is the stated combination of the search directions
+    # (4) the step is the stated combination of the search directions (bit for bit, from the device's own S and c: tests/test_hip_fit_stages.py)
     L = cg.iter_logs[-1]
     step = (cg.S[:, :2].astype('f8') @ L['c'][:2]).reshape(-1, 3)
     assert np.allclose(cg.fs - pos0, step, atol=1e-3)
