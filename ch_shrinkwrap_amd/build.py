@@ -38,6 +38,7 @@ OBJ_EVALUATION = _csrc('nw_evaluation.o')
 OBJ_SIMULATION = _csrc('nw_simulation.o')
 OBJ_DISTANCE = _csrc('nw_distance.o')
 OBJ_NEIGHBOURS = _csrc('nw_neighbours.o')
+OBJ_INTERSECTIONS = _csrc('nw_intersections.o')
 # the translation units of libnanowrap_hip.so: (source, object, what else it is rebuilt for, flags).  The objects are linked in this order.
 UNITS = [
     # the per-iteration kernels and the C-ABI; every header of csrc/ but nw_bq.h and nw_bq_core.h is included by it (directly or through
@@ -67,7 +68,10 @@ UNITS = [
     # the exact k-th-nearest-neighbour distance, for query lists and for the nodes of a voxel lattice (nw_neighbours_core.h: the list of
     # the k best, the ring bound and the quantisation, which the tests also compile for the CPU)
     (_csrc('nw_neighbours.hip'), OBJ_NEIGHBOURS, [_include('nw_neighbours.h'), _csrc('nw_neighbours_core.h')] + _BQ_H, _QUERY),
-    # what the seven above share (csrc/nw_bq.h): the exclusive scan and the point grid's bounding box and counting sort, float and double
+    # the self-intersection check: which pairs of faces cross (nw_intersections_core.h: the pair predicate, which the tests also compile
+    # for the CPU)
+    (_csrc('nw_intersections.hip'), OBJ_INTERSECTIONS, [_include('nw_intersections.h'), _csrc('nw_intersections_core.h')] + _BQ_H, _QUERY),
+    # what the eight above share (csrc/nw_bq.h): the exclusive scan and the point grid's bounding box and counting sort, float and double
     (_csrc('nw_bq.hip'), OBJ_BQ, _BQ, _QUERY),
 ]
 DEPS = sorted(set(d for src, _, extra, _ in UNITS for d in [src] + extra))
@@ -176,7 +180,15 @@ KERNEL_BUDGETS = {
     # never in a register array indexed at run time) and against silent growth
     'k_kn_queries':                   (64, 32 * 1024),     # LDS = 128 lanes x 32 slots x 8 bytes
     'k_kn_nodes':                     (64, 32 * 1024),
-    # what the seven units above share (csrc/nw_bq.o): the exclusive scan, and the point grid of hole punching (f32) and of the metric (f64)
+    # the self-intersection check (csrc/nw_intersections.o): an end-of-fit query in float64, budgeted for zero scratch (the corners of a
+    # shared-vertex pair are picked with selects, never from an array indexed at run time) and against silent growth
+    'k_mx_face_setup':                (64, 0),
+    'k_mx_rho_reduce':                (24, 64),            # LDS = the four waves' maxima and sums
+    'k_mx_count':                     (168, 0),            # the lane's own face in float64 (ids, corners, centroid, radius), the candidate's, and the predicate's two normals and triple products: 3 waves per SIMD
+    'k_mx_emit':                      (168, 0),
+    'k_mx_stats':                     (64, 0),             # the walk without the predicate
+    'k_mx_totals':                    (24, 128),           # LDS = the four waves' three sums
+    # what the eight units above share (csrc/nw_bq.o): the exclusive scan, and the point grid of hole punching (f32) and of the metric (f64)
     'k_bq_scan_tiles':                (32, 1024),
     'k_bq_scan_bsums':                (32, 1024),
     'k_bq_scan_final':                (32, 1024),
@@ -187,7 +199,7 @@ KERNEL_BUDGETS = {
     'k_bq_cell_count_f64':            (48, 0),
     'k_bq_scatter_f64':               (16, 0),
 }
-BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_DISTANCE, OBJ_NEIGHBOURS, OBJ_BQ]
+BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_DISTANCE, OBJ_NEIGHBOURS, OBJ_INTERSECTIONS, OBJ_BQ]
 
 
 def kernel_resources(obj=None):

@@ -308,13 +308,16 @@ def mesh_topology(faces, n_vertices=None):
     return dict(euler=surgery.euler_characteristic(f), manifold=bool(distinct and one_fan), border_loops=loops, twin=twin)
 
 
-def mesh_properties(mesh, label_faces='device', device=0):
+def mesh_properties(mesh, label_faces='device', device=0, self_intersections=False):
     """dict(euler, genus, manifold, components, area, volume) of a mesh with `vertices` / `faces` (or the reference's `_vertices['position']`).
     euler, manifold: mesh_topology.  components: edge-connected components of the faces.  genus: the sum of the components' genera,
     (2 components - euler - border loops) / 2 (a sphere 0, a torus 1, two spheres 0).  area and the signed volume (positive for a
     closed surface whose faces wind counter-clockwise seen from outside) are the sums over the components.
     label_faces='device': components, area and volume by nws_label_faces / nws_component_stats (include/nw_surgery.h); or a labeller
-    `label_faces(faces, twin, mask) -> (label, n)` (surgery.scipy_label_faces), with area and volume summed in NumPy float64."""
+    `label_faces(faces, twin, mask) -> (label, n)` (surgery.scipy_label_faces), with area and volume summed in NumPy float64.
+    self_intersections=True: two more entries, whether the surface is embedded as well as closed and manifold --
+    `self_intersections`, the number of pairs of faces that properly cross, and `self_intersecting_faces`, the faces in such a pair
+    (intersections.self_intersections, include/nw_intersections.h: on the device, no host fallback)."""
     from . import surgery
     pos = np.ascontiguousarray(mesh.vertices if hasattr(mesh, 'vertices') else mesh._vertices['position'], np.float32).reshape(-1, 3)
     faces = np.ascontiguousarray(mesh.faces, np.int32).reshape(-1, 3)
@@ -335,7 +338,12 @@ def mesh_properties(mesh, label_faces='device', device=0):
         area = float(0.5 * np.sqrt((np.cross(p1 - p0, p2 - p0) ** 2).sum(1)).sum())
         volume = float((p0 * np.cross(p1, p2)).sum() / 6.0)
     genus = (2 * int(n) - top['euler'] - top['border_loops']) // 2
-    return dict(euler=int(top['euler']), genus=int(genus), manifold=top['manifold'], components=int(n), area=area, volume=volume)
+    out = dict(euler=int(top['euler']), genus=int(genus), manifold=top['manifold'], components=int(n), area=area, volume=volume)
+    if self_intersections:
+        from .intersections import self_intersections as find
+        x = find((pos, faces), return_pairs=False, device=device)
+        out['self_intersections'], out['self_intersecting_faces'] = x['n_pairs'], x['n_faces']
+    return out
 
 
 # ---- recipe-module mirrors (recipe_modules/surface_feature_extraction.py:76-167) ------------------------------------------------------
@@ -395,18 +403,24 @@ class AverageSquaredDistance(_Module):
 
 class MeshProperties(_Module):
     """Mirror of the recipe module `MeshProperties` (:144-167): the mesh under `inputMesh` -> a one-row table euler genus manifold
-    components, and the two columns upstream has commented out: area, volume."""
+    components, and the two columns upstream has commented out: area, volume.  With self_intersections=True two more:
+    self_intersections (the crossing pairs of faces) and self_intersecting_faces."""
 
     def __init__(self, **kw):
         self.inputMesh, self.output = 'membrane', 'mesh_props'
         self.label_faces = 'device'                # not a trait upstream: see mesh_properties
+        self.self_intersections = False            # not a trait upstream: see mesh_properties
         self.device = 0
         self._set(kw)
 
     def run(self, inputMesh):
-        q = mesh_properties(inputMesh, label_faces=self.label_faces, device=self.device)
-        return {'euler': np.atleast_1d(q['euler']), 'genus': np.atleast_1d(q['genus']), 'manifold': np.atleast_1d(int(q['manifold'])),
-                'components': np.atleast_1d(q['components']), 'area': np.atleast_1d(q['area']), 'volume': np.atleast_1d(q['volume'])}
+        q = mesh_properties(inputMesh, label_faces=self.label_faces, device=self.device, self_intersections=bool(self.self_intersections))
+        table = {'euler': np.atleast_1d(q['euler']), 'genus': np.atleast_1d(q['genus']), 'manifold': np.atleast_1d(int(q['manifold'])),
+                 'components': np.atleast_1d(q['components']), 'area': np.atleast_1d(q['area']), 'volume': np.atleast_1d(q['volume'])}
+        for name in ('self_intersections', 'self_intersecting_faces'):
+            if name in q:
+                table[name] = np.atleast_1d(q[name])
+        return table
 
     def execute(self, namespace):
         table = self.run(namespace[self.inputMesh])

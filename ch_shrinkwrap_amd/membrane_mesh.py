@@ -64,6 +64,7 @@ class MembraneMesh(TriMesh):
         self.neck_remover = None      # None (selection only) | 'device' (remove_necks: guarded cut, repair, remesh) | callable(mesh, vertex_ids)
         self.hole_puncher = None      # None (no punching) | 'device' (punch_holes: point queries on the GPU) | callable(mesh, points, eps)
         self.edge_cleaner = None      # None | 'device' (remove_extra_short_edges at every remesh) | callable(mesh)
+        self.intersection_check = None  # None | 'device' (self_intersections at every block boundary and at the end of a fit -> intersection_log; observes only)
         # neck guard (remove_necks with neck_remover='device'): see _remove_necks_device
         self.neck_guard = True
         self.neck_max_regions = 32
@@ -76,6 +77,8 @@ class MembraneMesh(TriMesh):
         self.neck_log = []
         self.punch_log = []
         self.edge_log = []
+        self.intersection_log = []
+        self._intersections = None    # IntersectionContext (csrc/nw_intersections.hip), kept across the boundaries of a fit
         self._surgery = None          # SurgeryContext (csrc/nw_surgery.hip): labelling, component statistics, winding numbers, short edges
         self._holepunch = None        # HolePunchContext of the fit (the localizations' cell grid lives on the device beside _native's)
         self._holepunch_key = None
@@ -113,6 +116,27 @@ class MembraneMesh(TriMesh):
         if not (value is None or value == 'device' or (callable(value) and not isinstance(value, str))):
             raise ValueError("edge_cleaner must be None, 'device' or a callable(mesh)")
         self.__dict__['_edge_cleaner'] = value
+
+    @property
+    def intersection_check(self):
+        return self.__dict__.get('_intersection_check')
+
+    @intersection_check.setter
+    def intersection_check(self, value):
+        if not (value is None or value == 'device'):
+            raise ValueError("intersection_check must be None or 'device'")
+        self.__dict__['_intersection_check'] = value
+
+    def _log_intersections(self, done):
+        """intersection_check='device': the crossing pairs of the mesh as it stands, appended to intersection_log.  It reads positions and
+        faces and writes nothing: a fit with it is bit-identical to one without."""
+        if self.intersection_check != 'device':
+            return
+        from .intersections import IntersectionContext
+        if self._intersections is None:
+            self._intersections = IntersectionContext(self._device)
+        r = self._intersections.set_mesh(self.vertices, self.faces).find(return_pairs=False, return_count=False)
+        self.intersection_log.append(dict(iteration=int(done), n_pairs=r['n_pairs'], n_faces=r['n_faces']))
 
     def _topology_changed(self, vertices, faces, all_referenced=False, mean_edge=None):
         """Rebuild the half-edge tables for a new (vertices, faces) pair; the optimiser of the old topology is dropped."""
@@ -604,6 +628,7 @@ class MembraneMesh(TriMesh):
                 self.cg = None
                 self._host_mesh_changed()
             self.block_log.append(dict(iteration=done, target_length=float(target), mean_length=float(self._mean_edge_length)))
+        self._log_intersections(done)
 
     def opt_conjugate_gradient(self, points, sigma, max_iter=10, step_size=1.0, weights=None, **kwargs):
         """_membrane_mesh.pyx:1427-1560: blocks of iterations on a fixed topology, mesh surgery between them."""
@@ -618,7 +643,9 @@ class MembraneMesh(TriMesh):
         done = 0
         self._in_fit = True
         try:
-            return self._run_blocks(points, lams, s, weights, plan)
+            done = self._run_blocks(points, lams, s, weights, plan)
+            self._log_intersections(done)                  # the end of the fit
+            return done
         finally:
             self._in_fit = False
             # (the device copy mirrors the mesh only until the caller touches it: the next curvature read or remesh starts from the host)
@@ -724,6 +751,7 @@ class ShrinkwrapMembrane(object):
         self.hole_puncher = None                   # not a trait upstream: 'device' = punch_holes with the point queries on the GPU (include/nw_holepunch.h); None = punch_frequency does nothing
         self.neck_remover = None                   # not a trait upstream: 'device' = remove_necks cuts guarded necks (include/nw_surgery.h); None = the neck traits only select
         self.edge_cleaner = None                   # not a trait upstream: 'device' = remove_extra_short_edges at every remesh; None = not run
+        self.intersection_check = None             # not a trait upstream: 'device' = the crossing face pairs at every block boundary and at the end -> mesh.intersection_log (include/nw_intersections.h); observes only
         self.remesher = 'device'                   # not a trait upstream (PYME always remeshes): 'device' = this package's remesher on the GPU (nw_remesh_device), 'builtin' = the same algorithm on the host (nwr_remesh), None holds the topology fixed
         for k, v in kw.items():
             if not hasattr(self, k):
@@ -735,6 +763,8 @@ class ShrinkwrapMembrane(object):
             v = getattr(self, name)
             if not (v is None or v == 'device' or (callable(v) and not isinstance(v, str))):
                 raise ValueError("%s must be None, 'device' or a callable" % name)
+        if not (self.intersection_check is None or self.intersection_check == 'device'):
+            raise ValueError("intersection_check must be None or 'device'")
 
     def execute(self, namespace):
         import time
@@ -747,7 +777,8 @@ class ShrinkwrapMembrane(object):
                             delaunay_eps=self.min_hole_radius, neck_threshold_low=self.neck_threshold_low,
                             neck_threshold_high=self.neck_threshold_high, neck_first_iter=self.neck_first_iter,
                             shrink_weight=self.shrink_weight, truncate_at=self.truncate_at, remesher=self.remesher,
-                            hole_puncher=self.hole_puncher, neck_remover=self.neck_remover, edge_cleaner=self.edge_cleaner)
+                            hole_puncher=self.hole_puncher, neck_remover=self.neck_remover, edge_cleaner=self.edge_cleaner,
+                            intersection_check=self.intersection_check)
         namespace[self.output] = mesh
         src = namespace[self.points]
         pts = np.ascontiguousarray(np.vstack([src['x'], src['y'], src['z']]).T)

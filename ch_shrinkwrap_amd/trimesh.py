@@ -471,6 +471,12 @@ class TriMesh(object):
         from .distance import distance_to_mesh
         return distance_to_mesh(points, self, **kw)
 
+    def self_intersections(self, **kw):
+        """The pairs of this mesh's faces that properly cross each other: intersections.self_intersections(self, **kw) -> dict(n_pairs,
+        n_faces, count, pairs) (on the device; raises without a GPU)."""
+        from .intersections import self_intersections
+        return self_intersections(self, **kw)
+
     # -- what upstream's MeshProperties module reads (evaluation.mesh_properties has the definitions).  None of them is a stored field:
     # each is computed from the face array when it is asked for and kept until the face array is replaced (a TriMesh's topology is
     # fixed: a remesher makes a new TriMesh).  euler and manifold are host work (twins and two connected-components passes, O(faces));
