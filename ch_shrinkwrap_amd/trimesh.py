@@ -477,6 +477,12 @@ class TriMesh(object):
         from .intersections import self_intersections
         return self_intersections(self, **kw)
 
+    def thickness(self, **kw):
+        """The local thickness of the structure this mesh encloses, per vertex: rays.thickness(self, **kw) -> dict(thickness, n_valid,
+        face) (rays along the inward normals cast on the device; raises without a GPU)."""
+        from .rays import thickness
+        return thickness(self, **kw)
+
     # -- what upstream's MeshProperties module reads (evaluation.mesh_properties has the definitions).  None of them is a stored field:
     # each is computed from the face array when it is asked for and kept until the face array is replaced (a TriMesh's topology is
     # fixed: a remesher makes a new TriMesh).  euler and manifold are host work (twins and two connected-components passes, O(faces));
