@@ -40,6 +40,7 @@ OBJ_DISTANCE = _csrc('nw_distance.o')
 OBJ_NEIGHBOURS = _csrc('nw_neighbours.o')
 OBJ_INTERSECTIONS = _csrc('nw_intersections.o')
 OBJ_RAYS = _csrc('nw_rays.o')
+OBJ_VOLUME = _csrc('nw_volume.o')
 # the translation units of libnanowrap_hip.so: (source, object, what else it is rebuilt for, flags).  The objects are linked in this order.
 UNITS = [
     # the per-iteration kernels and the C-ABI; every header of csrc/ but nw_bq.h and nw_bq_core.h is included by it (directly or through
@@ -75,7 +76,10 @@ UNITS = [
     # ray casting against the mesh: local thickness and the parity side test (nw_rays_core.h: the ray-face test and the walk along the
     # ray, which the tests also compile for the CPU; it uses nw_intersections_core.h's vectors and centroids)
     (_csrc('nw_rays.hip'), OBJ_RAYS, [_include('nw_rays.h'), _csrc('nw_rays_core.h'), _csrc('nw_intersections_core.h')] + _BQ_H, _QUERY),
-    # what the nine above share (csrc/nw_bq.h): the exclusive scan and the point grid's bounding box and counting sort, float and double
+    # the banded signed-distance volume of the mesh on a voxel lattice (nw_volume_core.h: the node position, the capped walk, the band
+    # rule, the predecessor rule and the quantisation, which the tests also compile for the CPU; it includes nw_distance_core.h)
+    (_csrc('nw_volume.hip'), OBJ_VOLUME, [_include('nw_volume.h'), _csrc('nw_volume_core.h'), _csrc('nw_distance_core.h')] + _BQ_H, _QUERY),
+    # what the ten above share (csrc/nw_bq.h): the exclusive scan and the point grid's bounding box and counting sort, float and double
     (_csrc('nw_bq.hip'), OBJ_BQ, _BQ, _QUERY),
 ]
 DEPS = sorted(set(d for src, _, extra, _ in UNITS for d in [src] + extra))
@@ -198,7 +202,15 @@ KERNEL_BUDGETS = {
     'k_rc_first':                     (128, 0),            # the ray, the piece, the candidate's centroid and one exact test in flight: 4 waves per SIMD (some of the walk's uniform values sit in VGPR lanes: no scratch)
     'k_rc_count':                     (128, 0),            # the same walk without the early exit, and the count: 4 waves per SIMD
     'k_rc_totals':                    (24, 96),            # LDS = the four waves' three sums
-    # what the nine units above share (csrc/nw_bq.o): the exclusive scan, and the point grid of hole punching (f32) and of the metric (f64)
+    # the signed-distance volume (csrc/nw_volume.o): the query's walk with a band, one lane per lattice node; no atomics, zero scratch
+    'k_vx_face_setup':                (64, 0),
+    'k_vx_rho_reduce':                (24, 64),            # LDS = the four waves' maxima and sums
+    'k_vx_nodes':                     (128, 192),          # k_md_query's record and walk, the band and six counters: 4 waves per SIMD; LDS = the four waves' six counters
+    'k_vx_seed':                      (128, 64),           # one exact test in flight; LDS = the four waves' (d2, face)
+    'k_vx_sweep':                     (24, 0),
+    'k_vx_finish':                    (16, 0),
+    'k_vx_totals':                    (32, 192),           # LDS = the four waves' six counters
+    # what the ten units above share (csrc/nw_bq.o): the exclusive scan, and the point grid of hole punching (f32) and of the metric (f64)
     'k_bq_scan_tiles':                (32, 1024),
     'k_bq_scan_bsums':                (32, 1024),
     'k_bq_scan_final':                (32, 1024),
@@ -209,7 +221,7 @@ KERNEL_BUDGETS = {
     'k_bq_cell_count_f64':            (48, 0),
     'k_bq_scatter_f64':               (16, 0),
 }
-BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_DISTANCE, OBJ_NEIGHBOURS, OBJ_INTERSECTIONS, OBJ_RAYS, OBJ_BQ]
+BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_DISTANCE, OBJ_NEIGHBOURS, OBJ_INTERSECTIONS, OBJ_RAYS, OBJ_VOLUME, OBJ_BQ]
 
 
 def kernel_resources(obj=None):

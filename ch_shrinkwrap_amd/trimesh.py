@@ -483,6 +483,23 @@ class TriMesh(object):
         from .rays import thickness
         return thickness(self, **kw)
 
+    def signed_distance_volume(self, voxel_size, **kw):
+        """The banded exact signed distance to this mesh on a voxel lattice: volume.signed_distance_volume(self, voxel_size, **kw) ->
+        dict(sd, face, mask, lo, h, dims, d_cap) (on the device; raises without a GPU)."""
+        from .volume import signed_distance_volume
+        return signed_distance_volume(self, voxel_size, **kw)
+
+    def voxelize(self, voxel_size, **kw):
+        """The bool mask [z, y, x] of the lattice nodes inside this closed mesh: volume.voxelize(self, voxel_size, **kw)."""
+        from .volume import voxelize
+        return voxelize(self, voxel_size, **kw)
+
+    def offset_surface(self, offset, **kw):
+        """The surface at signed distance `offset` from this closed mesh (positive: outwards): volume.offset_surface(self, offset, **kw)
+        -> isosurface.Surface."""
+        from .volume import offset_surface
+        return offset_surface(self, offset, **kw)
+
     # -- what upstream's MeshProperties module reads (evaluation.mesh_properties has the definitions).  None of them is a stored field:
     # each is computed from the face array when it is asked for and kept until the face array is replaced (a TriMesh's topology is
     # fixed: a remesher makes a new TriMesh).  euler and manifold are host work (twins and two connected-components passes, O(faces));
