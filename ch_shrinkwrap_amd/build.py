@@ -41,6 +41,7 @@ OBJ_NEIGHBOURS = _csrc('nw_neighbours.o')
 OBJ_INTERSECTIONS = _csrc('nw_intersections.o')
 OBJ_RAYS = _csrc('nw_rays.o')
 OBJ_VOLUME = _csrc('nw_volume.o')
+OBJ_PROXIMITY = _csrc('nw_proximity.o')
 # the translation units of libnanowrap_hip.so: (source, object, what else it is rebuilt for, flags).  The objects are linked in this order.
 UNITS = [
     # the per-iteration kernels and the C-ABI; every header of csrc/ but nw_bq.h and nw_bq_core.h is included by it (directly or through
@@ -79,7 +80,12 @@ UNITS = [
     # the banded signed-distance volume of the mesh on a voxel lattice (nw_volume_core.h: the node position, the capped walk, the band
     # rule, the predecessor rule and the quantisation, which the tests also compile for the CPU; it includes nw_distance_core.h)
     (_csrc('nw_volume.hip'), OBJ_VOLUME, [_include('nw_volume.h'), _csrc('nw_volume_core.h'), _csrc('nw_distance_core.h')] + _BQ_H, _QUERY),
-    # what the ten above share (csrc/nw_bq.h): the exclusive scan and the point grid's bounding box and counting sort, float and double
+    # the exact distance between two meshes, per face of one of them (nw_proximity_core.h: the triangle-triangle distance and the capped
+    # walk of a face over the other mesh's centroid grid, which the tests also compile for the CPU; it includes nw_distance_core.h and
+    # nw_intersections_core.h)
+    (_csrc('nw_proximity.hip'), OBJ_PROXIMITY, [_include('nw_proximity.h'), _csrc('nw_proximity_core.h'), _csrc('nw_distance_core.h'),
+                                                _csrc('nw_intersections_core.h')] + _BQ_H, _QUERY),
+    # what the eleven above share (csrc/nw_bq.h): the exclusive scan and the point grid's bounding box and counting sort, float and double
     (_csrc('nw_bq.hip'), OBJ_BQ, _BQ, _QUERY),
 ]
 DEPS = sorted(set(d for src, _, extra, _ in UNITS for d in [src] + extra))
@@ -210,7 +216,15 @@ KERNEL_BUDGETS = {
     'k_vx_sweep':                     (24, 0),
     'k_vx_finish':                    (16, 0),
     'k_vx_totals':                    (32, 192),           # LDS = the four waves' six counters
-    # what the ten units above share (csrc/nw_bq.o): the exclusive scan, and the point grid of hole punching (f32) and of the metric (f64)
+    # the mesh-to-mesh distance (csrc/nw_proximity.o): the query's walk with a band, one lane per face of the querying mesh; no atomics of its
+    # own, zero scratch (the corners of a candidate and of the 3 x 3 edge pairs are picked with selects inside loops that stay loops, never from an array
+    # indexed at run time)
+    'k_mm_face_setup':                (56, 0),
+    'k_mm_rho_reduce':                (24, 64),            # LDS = the four waves' maxima and sums
+    'k_mm_query':                     (168, 160),          # the lane's face (centroid, radius, corner pointers), the walk's cell ranges and (d2, face), both triangles in float64 with their normals and one point-triangle or edge-edge candidate in flight: 3 waves per SIMD (amdgpu_waves_per_eu(3, 8)); LDS = the four waves' five counters
+    'k_mm_finish':                    (136, 0),            # one pair test with its kind and two closest points: 3 waves per SIMD
+    'k_mm_totals':                    (32, 160),           # LDS = the four waves' five counters
+    # what the eleven units above share (csrc/nw_bq.o): the exclusive scan, and the point grid of hole punching (f32) and of the metric (f64)
     'k_bq_scan_tiles':                (32, 1024),
     'k_bq_scan_bsums':                (32, 1024),
     'k_bq_scan_final':                (32, 1024),
@@ -221,7 +235,7 @@ KERNEL_BUDGETS = {
     'k_bq_cell_count_f64':            (48, 0),
     'k_bq_scatter_f64':               (16, 0),
 }
-BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_DISTANCE, OBJ_NEIGHBOURS, OBJ_INTERSECTIONS, OBJ_RAYS, OBJ_VOLUME, OBJ_BQ]
+BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_DISTANCE, OBJ_NEIGHBOURS, OBJ_INTERSECTIONS, OBJ_RAYS, OBJ_VOLUME, OBJ_PROXIMITY, OBJ_BQ]
 
 
 def kernel_resources(obj=None):

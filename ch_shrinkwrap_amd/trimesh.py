@@ -500,6 +500,12 @@ class TriMesh(object):
         from .volume import offset_surface
         return offset_surface(self, offset, **kw)
 
+    def distance_to_mesh_of(self, other, band=np.inf, **kw):
+        """The exact distance of every face of this mesh from another mesh's triangles: proximity.mesh_distance(self, other, band, **kw)
+        -> dict(distance, partner, kind[, closest_a, closest_b], info) (on the device; raises without a GPU)."""
+        from .proximity import mesh_distance
+        return mesh_distance(self, other, band=band, **kw)
+
     # -- what upstream's MeshProperties module reads (evaluation.mesh_properties has the definitions).  None of them is a stored field:
     # each is computed from the face array when it is asked for and kept until the face array is replaced (a TriMesh's topology is
     # fixed: a remesher makes a new TriMesh).  euler and manifold are host work (twins and two connected-components passes, O(faces));
