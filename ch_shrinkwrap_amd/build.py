@@ -42,6 +42,7 @@ OBJ_INTERSECTIONS = _csrc('nw_intersections.o')
 OBJ_RAYS = _csrc('nw_rays.o')
 OBJ_VOLUME = _csrc('nw_volume.o')
 OBJ_PROXIMITY = _csrc('nw_proximity.o')
+OBJ_MAPPING = _csrc('nw_mapping.o')
 # the translation units of libnanowrap_hip.so: (source, object, what else it is rebuilt for, flags).  The objects are linked in this order.
 UNITS = [
     # the per-iteration kernels and the C-ABI; every header of csrc/ but nw_bq.h and nw_bq_core.h is included by it (directly or through
@@ -85,8 +86,14 @@ UNITS = [
     # nw_intersections_core.h)
     (_csrc('nw_proximity.hip'), OBJ_PROXIMITY, [_include('nw_proximity.h'), _csrc('nw_proximity_core.h'), _csrc('nw_distance_core.h'),
                                                 _csrc('nw_intersections_core.h')] + _BQ_H, _QUERY),
-    # what the eleven above share (csrc/nw_bq.h): the exclusive scan and the point grid's bounding box and counting sort, float and double
+    # what the eleven above share (csrc/nw_bq.h), and the one below them: the exclusive scan and the point grid's bounding box and
+    # counting sort, float and double
     (_csrc('nw_bq.hip'), OBJ_BQ, _BQ, _QUERY),
+    # localizations mapped onto the mesh: per-vertex mass, per-face counts and value sums as integers (nw_mapping_core.h: the weights, the
+    # quantisation, the limbs and the vertex areas, which the tests also compile for the CPU; it includes nw_volume_core.h for the capped
+    # walk and through it nw_distance_core.h)
+    (_csrc('nw_mapping.hip'), OBJ_MAPPING, [_include('nw_mapping.h'), _csrc('nw_mapping_core.h'), _csrc('nw_volume_core.h'),
+                                            _csrc('nw_distance_core.h')] + _BQ_H, _QUERY),
 ]
 DEPS = sorted(set(d for src, _, extra, _ in UNITS for d in [src] + extra))
 
@@ -224,7 +231,13 @@ KERNEL_BUDGETS = {
     'k_mm_query':                     (168, 160),          # the lane's face (centroid, radius, corner pointers), the walk's cell ranges and (d2, face), both triangles in float64 with their normals and one point-triangle or edge-edge candidate in flight: 3 waves per SIMD (amdgpu_waves_per_eu(3, 8)); LDS = the four waves' five counters
     'k_mm_finish':                    (136, 0),            # one pair test with its kind and two closest points: 3 waves per SIMD
     'k_mm_totals':                    (32, 160),           # LDS = the four waves' five counters
-    # what the eleven units above share (csrc/nw_bq.o): the exclusive scan, and the point grid of hole punching (f32) and of the metric (f64)
+    # localizations on the mesh (csrc/nw_mapping.o): the volume unit's walk with one lane per localization, then integer atomics whose
+    # results are not read; zero scratch (the weights are written with constant indices, the corners' atomics are spelled out)
+    'k_lm_face_setup':                (64, 0),
+    'k_lm_rho_reduce':                (24, 64),            # LDS = the four waves' maxima and sums
+    'k_lm_map':                       (128, 96),           # k_vx_nodes' record and walk, the weights and one product's limbs: 4 waves per SIMD; LDS = the four waves' three counters
+    'k_lm_totals':                    (32, 96),            # LDS = the four waves' three counters
+    # what the eleven units above share (csrc/nw_bq.o), and nw_mapping.o: the exclusive scan, and the point grid of hole punching (f32) and of the metric (f64)
     'k_bq_scan_tiles':                (32, 1024),
     'k_bq_scan_bsums':                (32, 1024),
     'k_bq_scan_final':                (32, 1024),
@@ -235,7 +248,7 @@ KERNEL_BUDGETS = {
     'k_bq_cell_count_f64':            (48, 0),
     'k_bq_scatter_f64':               (16, 0),
 }
-BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_DISTANCE, OBJ_NEIGHBOURS, OBJ_INTERSECTIONS, OBJ_RAYS, OBJ_VOLUME, OBJ_PROXIMITY, OBJ_BQ]
+BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_DISTANCE, OBJ_NEIGHBOURS, OBJ_INTERSECTIONS, OBJ_RAYS, OBJ_VOLUME, OBJ_PROXIMITY, OBJ_MAPPING, OBJ_BQ]
 
 
 def kernel_resources(obj=None):

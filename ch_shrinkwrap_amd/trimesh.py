@@ -506,6 +506,12 @@ class TriMesh(object):
         from .proximity import mesh_distance
         return mesh_distance(self, other, band=band, **kw)
 
+    def surface_density(self, points, band=30.0, **kw):
+        """The density of a localization cloud on this mesh, per vertex: mapping.surface_density(points, self, band, **kw)
+        -> dict(density, n, area, count, means, n_in_band, n_total) (on the device; raises without a GPU)."""
+        from .mapping import surface_density
+        return surface_density(points, self, band=band, **kw)
+
     # -- what upstream's MeshProperties module reads (evaluation.mesh_properties has the definitions).  None of them is a stored field:
     # each is computed from the face array when it is asked for and kept until the face array is replaced (a TriMesh's topology is
     # fixed: a remesher makes a new TriMesh).  euler and manifold are host work (twins and two connected-components passes, O(faces));
