@@ -43,6 +43,7 @@ OBJ_RAYS = _csrc('nw_rays.o')
 OBJ_VOLUME = _csrc('nw_volume.o')
 OBJ_PROXIMITY = _csrc('nw_proximity.o')
 OBJ_MAPPING = _csrc('nw_mapping.o')
+OBJ_CLUSTERING = _csrc('nw_clustering.o')
 # the translation units of libnanowrap_hip.so: (source, object, what else it is rebuilt for, flags).  The objects are linked in this order.
 UNITS = [
     # the per-iteration kernels and the C-ABI; every header of csrc/ but nw_bq.h and nw_bq_core.h is included by it (directly or through
@@ -86,7 +87,7 @@ UNITS = [
     # nw_intersections_core.h)
     (_csrc('nw_proximity.hip'), OBJ_PROXIMITY, [_include('nw_proximity.h'), _csrc('nw_proximity_core.h'), _csrc('nw_distance_core.h'),
                                                 _csrc('nw_intersections_core.h')] + _BQ_H, _QUERY),
-    # what the eleven above share (csrc/nw_bq.h), and the one below them: the exclusive scan and the point grid's bounding box and
+    # what the eleven above share (csrc/nw_bq.h), and the two below them: the exclusive scan and the point grid's bounding box and
     # counting sort, float and double
     (_csrc('nw_bq.hip'), OBJ_BQ, _BQ, _QUERY),
     # localizations mapped onto the mesh: per-vertex mass, per-face counts and value sums as integers (nw_mapping_core.h: the weights, the
@@ -94,6 +95,11 @@ UNITS = [
     # walk and through it nw_distance_core.h)
     (_csrc('nw_mapping.hip'), OBJ_MAPPING, [_include('nw_mapping.h'), _csrc('nw_mapping_core.h'), _csrc('nw_volume_core.h'),
                                             _csrc('nw_distance_core.h')] + _BQ_H, _QUERY),
+    # DBSCAN clustering of the cloud: neighbour counts, core points, clusters, border points (nw_clustering_core.h: near, the walk, the
+    # guard of the two shortcuts and the three visitors, which the tests also compile for the CPU; it includes nw_neighbours_core.h for
+    # the squared distance and the ring bound)
+    (_csrc('nw_clustering.hip'), OBJ_CLUSTERING, [_include('nw_clustering.h'), _csrc('nw_clustering_core.h'), _csrc('nw_neighbours_core.h')] + _BQ_H,
+     _QUERY),
 ]
 DEPS = sorted(set(d for src, _, extra, _ in UNITS for d in [src] + extra))
 
@@ -237,6 +243,16 @@ KERNEL_BUDGETS = {
     'k_lm_rho_reduce':                (24, 64),            # LDS = the four waves' maxima and sums
     'k_lm_map':                       (128, 96),           # k_vx_nodes' record and walk, the weights and one product's limbs: 4 waves per SIMD; LDS = the four waves' three counters
     'k_lm_totals':                    (32, 96),            # LDS = the four waves' three counters
+    # DBSCAN clustering (csrc/nw_clustering.o): one lane per point in cell order, the walk's visitor in registers; zero scratch.  All of them
+    # reach 8 waves per SIMD (512 // VGPRs, capped at 8) with room to the next step at 64
+    'k_pc_order':                     (16, 0),
+    'k_pc_count':                     (56, 64),            # the point in float64, the walk's ranges and two counters: 8 waves per SIMD; LDS = the four waves' two counters
+    'k_pc_hook':                      (56, 64),            # the same walk and the two roots of a union: 8 waves per SIMD
+    'k_pc_compress':                  (16, 0),
+    'k_pc_number':                    (16, 0),
+    'k_pc_border':                    (56, 64),            # the same walk and the best (d2, index): 8 waves per SIMD
+    'k_pc_stats':                     (40, 96),            # eight values through the wave's butterflies: 8 waves per SIMD; LDS = the four waves' three counters
+    'k_pc_totals':                    (64, 256),           # eight 64-bit sums per thread, one workgroup: 8 waves per SIMD; LDS = the four waves' eight counters
     # what the eleven units above share (csrc/nw_bq.o), and nw_mapping.o: the exclusive scan, and the point grid of hole punching (f32) and of the metric (f64)
     'k_bq_scan_tiles':                (32, 1024),
     'k_bq_scan_bsums':                (32, 1024),
@@ -248,7 +264,7 @@ KERNEL_BUDGETS = {
     'k_bq_cell_count_f64':            (48, 0),
     'k_bq_scatter_f64':               (16, 0),
 }
-BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_DISTANCE, OBJ_NEIGHBOURS, OBJ_INTERSECTIONS, OBJ_RAYS, OBJ_VOLUME, OBJ_PROXIMITY, OBJ_MAPPING, OBJ_BQ]
+BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_DISTANCE, OBJ_NEIGHBOURS, OBJ_INTERSECTIONS, OBJ_RAYS, OBJ_VOLUME, OBJ_PROXIMITY, OBJ_MAPPING, OBJ_CLUSTERING, OBJ_BQ]
 
 
 def kernel_resources(obj=None):

@@ -17,6 +17,8 @@ case "${1:-cpu}" in
     python -m pytest tests/test_mesh_proximity_ref.py tests/test_proximity_core_cpu.py tests/test_proximity_device_abi.py -q
     # the localization mapping alone: restatement, compiled core (also under the sanitizers), ABI
     python -m pytest tests/test_surface_mapping_ref.py tests/test_mapping_core_cpu.py tests/test_mapping_device_abi.py -q
+    # DBSCAN clustering alone: restatement (against scikit-learn), compiled core (also under the sanitizers), ABI
+    python -m pytest tests/test_dbscan_ref.py tests/test_clustering_core_cpu.py tests/test_clustering_device_abi.py -q
     ;;
   gpu)
     timeout -k 10 900 python -m pytest tests -x -q -m gpu
@@ -25,6 +27,7 @@ case "${1:-cpu}" in
     timeout -k 10 600 python tools/volume_profile.py c3
     timeout -k 10 600 python tools/proximity_profile.py
     timeout -k 10 600 python tools/mapping_profile.py
+    timeout -k 10 600 python tools/clustering_profile.py c3 1.0
     ;;
   profile)
     tools/profile_round.sh "${2:?tag}"
