@@ -147,6 +147,13 @@ KERNEL_BUDGETS = {
     'k_prior_directions':             (96, 1024),          # streaming since the ring half left it: 5 waves per SIMD
     'k_subspace_point_sums':          (128, 1024),         # 4 waves per SIMD cover the launch in one round (rows of two localizations in flight)
     'k_solve_update':                 (128, 1024),
+    # the k-d work list of the query (csrc/nw_partition.h): once per cloud, budgeted for zero scratch and against silent growth
+    'k_kd_block_max':                 (16, 0),
+    'k_kd_seg_counts':                (16, 0),
+    'k_kd_fill_segs':                 (32, 0),
+    'k_kd_leaf_counts':               (16, 0),
+    'k_kd_fill_leaves':               (32, 0),
+    'k_kd_partition':                 (64, 146 * 1024),    # two position lists (16 bits) and the composites of 16384 localizations, 512 boxes, a histogram: one workgroup of 1024 per CU
     # hole punching (csrc/nw_holepunch.o): block-boundary queries, budgeted for zero scratch and against silent growth
     'k_hp_empty_faces':               (64, 0),
     'k_hp_pair':                      (64, 8 * 1024),      # two LDS tiles of 256 float4 (centroids, normals)

@@ -16,6 +16,7 @@
 
 #include "../../include/nanowrap.h"
 #include "nw_kernels.h"
+#include "nw_partition.h"       // the balanced k-d work list of the query (rules: nw_partition_core.h, plain C++, tested on the CPU)
 #include "nw_host_copy.h"       // the copy threads (NwHostPool), the row copier and the chunked copy-out: plain host C++, tested on the CPU
 
 // stable LSD radix sort of (key, value) pairs on the device (csrc/nw_sort.hip, hipCUB); returns a hipError_t as int
@@ -173,7 +174,13 @@ struct nw_ctx {
     DevBuf<unsigned long long> nn_stats;   // developer counters of the NN query (nw_debug, what = 0); null unless enabled
     DevBuf<unsigned> proj_key;        // projection keys of the last completed query (second sort, see k_projection_keys)
     DevBuf<int> proj_idx;
+    DevBuf<float4> proj_foot;         // ... and the foot point and signed height of every localization (the k-d work list's coordinates)
     bool proj_ready = false, proj_sorted = false;
+    DevBuf<NwItem> kd_leaves;         // the k-d work list cut by the second sort (kd_partition): build_items installs it whatever the level
+    int kd_nleaves = 0, kd_leaf = 0, kd_nsegs = 0, kd_level = 0;
+    std::vector<uint32_t> kd_dbg_key; // NW_KD_KEEP (developer aid, nw_debug what = 5, 6): what the partition was given, in key order
+    std::vector<float> kd_dbg_foot;
+    std::vector<int> kd_dbg_face, kd_dbg_perm;
     bool face_warm = false;           // `face` holds the previous iteration's nearest faces of THIS topology (warm start)
 
     // mesh
@@ -391,13 +398,43 @@ int ensure_item_done(nw_ctx *ctx)
     return NW_OK;
 }
 
+// localizations per wave: 64 when that still gives every SIMD several waves; a small cloud is cut finer (more, lighter waves: the
+// launch then ends with its slowest wave, and a wave's candidate set shrinks with its patch)
+static int wanted_item_points(const nw_ctx *ctx)
+{
+    int ipts = (ctx->N >= 64 * 9216) ? NW_ITEM_POINTS : NW_ITEM_POINTS / 2;       // 9216 = 1.5 waves for each of the 256 x 4 x 6 wave slots
+    if (const char *e = getenv("NW_ITEM_PTS")) ipts = std::max(8, std::min(NW_ITEM_POINTS, atoi(e)));
+    return ipts;
+}
+
+// what every new work list needs beside the items themselves
+static int finish_items(nw_ctx *ctx, int nitems, int level)
+{
+    ctx->nitems = nitems;
+    ctx->item_level = level;
+    NW_HIP(ctx->item_cost.ensure((size_t)2 * nitems));        // (second half: start times, developer aid NW_ITEM_TIMES)
+    NW_HIP(hipMemsetAsync(ctx->item_cost.p, 0, (size_t)2 * nitems * sizeof(unsigned), ctx->stream));
+    NW_TRY(ensure_item_done(ctx));
+    ctx->items_by_cost = false; ctx->item_cost_valid = false;
+    return NW_OK;
+}
+
 int build_items(nw_ctx *ctx, int level)
 {
     const int64_t N = ctx->N;
-    // localizations per wave: 64 when that still gives every SIMD several waves; a small cloud is cut finer (more, lighter waves: the
-    // launch then ends with its slowest wave, and a wave's candidate set shrinks with its patch)
-    int ipts = (N >= 64 * 9216) ? NW_ITEM_POINTS : NW_ITEM_POINTS / 2;       // 9216 = 1.5 waves for each of the 256 x 4 x 6 wave slots
-    if (const char *e = getenv("NW_ITEM_PTS")) ipts = std::max(8, std::min(NW_ITEM_POINTS, atoi(e)));
+    const int ipts = wanted_item_points(ctx);
+    if (ctx->kd_nleaves > 0 && ipts == ctx->kd_leaf) {
+        // after the second sort the list is the k-d's leaves (kd_partition), whatever the level: a new cell size changes the grid only
+        if (ctx->nitems > 0 && ctx->item_level >= 0 && ipts == ctx->item_points) { ctx->item_level = level; return NW_OK; }
+        ctx->item_points = ipts;
+        NW_HIP(ctx->items.ensure((size_t)ctx->kd_nleaves));
+        NW_HIP(hipMemcpyAsync(ctx->items.p, ctx->kd_leaves.p, (size_t)ctx->kd_nleaves * sizeof(NwItem), hipMemcpyDeviceToDevice, ctx->stream));
+        NW_TRY(finish_items(ctx, ctx->kd_nleaves, level));
+        if (getenv("NW_VERBOSE"))
+            fprintf(stderr, "[nanowrap] work list: k-d leaves of %d start segments (Morton level %d), %d items (%.1f localizations per wave)\n", ctx->kd_nsegs,
+                    ctx->kd_level, ctx->nitems, (double)N / std::max(ctx->nitems, 1));
+        return NW_OK;
+    }
     if (level == ctx->item_level && ctx->nitems > 0 && ipts == ctx->item_points) return NW_OK;
     ctx->item_points = ipts;
     DevBuf<int> head, hscan, bstart, icount, istart;
@@ -418,12 +455,7 @@ int build_items(nw_ctx *ctx, int level)
     hipLaunchKernelGGL(k_block_fill_items, dim3(nblk(nblocks)), dim3(NW_BLOCK), 0, ctx->stream, bstart.p, istart.p, nblocks, ctx->items.p, ctx->item_points);
     NW_HIP(hipGetLastError());
     NW_HIP(hipStreamSynchronize(ctx->stream));          // the temporaries die with this scope
-    ctx->nitems = nitems;
-    ctx->item_level = level;
-    NW_HIP(ctx->item_cost.ensure((size_t)2 * nitems));        // (second half: start times, developer aid NW_ITEM_TIMES)
-    NW_HIP(hipMemsetAsync(ctx->item_cost.p, 0, (size_t)2 * nitems * sizeof(unsigned), ctx->stream));
-    NW_TRY(ensure_item_done(ctx));
-    ctx->items_by_cost = false; ctx->item_cost_valid = false;
+    NW_TRY(finish_items(ctx, nitems, level));
     if (getenv("NW_VERBOSE"))
         fprintf(stderr, "[nanowrap] work list: Morton level %d (block %.2f), %d blocks, %d items (%.1f localizations per wave)\n", level,
                 ctx->morton_unit * (float)(1 << level), nblocks, nitems, (double)N / std::max(nitems, 1));
@@ -806,6 +838,7 @@ NW_EXPORT int nw_set_points(nw_ctx *ctx, const float *xyz, int64_t n_points, con
     ctx->face_warm = false;
     if (verbose_level() >= 2) fprintf(stderr, "[nanowrap] warm start dropped (%s)\n", __func__);
     ctx->proj_ready = false; ctx->proj_sorted = false;
+    ctx->kd_nleaves = 0;
     ctx->tuned = false; ctx->cell_tune = 1.0; ctx->blocks_done = 0;
     ctx->last_mean_dist = -1.0;
     ctx->searched = false;
@@ -1231,6 +1264,88 @@ NW_EXPORT int nw_reset_history(nw_ctx *ctx)
 // Second sort of the localizations, by the foot point on the surface (k_projection_keys): once per cloud, at the start of the
 // first block after a completed query.  Everything per-localization that survives a block boundary moves along; the cached
 // weight matrix / residual of the previous block (cg.w, cg.res, Afunc/Ahfunc) are recomputed by the block that starts now.
+// NW_KD_SORT=0: the list is cut from the sorted keys alone, as before the first completed query; NW_KD_HEIGHT: weight of the signed height
+static bool kd_sort_on()
+{
+    static const bool on = [] { const char *e = getenv("NW_KD_SORT"); return e ? atoi(e) != 0 : true; }();
+    return on;
+}
+static float kd_height_weight()
+{
+    static const float w = [] { const char *e = getenv("NW_KD_HEIGHT"); return e ? (float)atof(e) : 0.5f; }();
+    return w;
+}
+
+// The balanced k-d partition of the key-sorted list (nw_partition_core.h): `order` (position -> current slot) comes back with every
+// start segment partitioned, and ctx->kd_leaves holds the work list that goes with it.
+static int kd_partition(nw_ctx *ctx, DevBuf<int> &order)
+{
+    const int N = (int)ctx->N;
+    const int leaf = wanted_item_points(ctx);
+    ctx->kd_nleaves = 0;
+    if (N < 1 || leaf < NWP_MIN_LEAF || leaf % 4 != 0 || !ctx->proj_foot.p) return NW_OK;
+    const int cap = NWP_CAP / leaf * leaf;
+    const float w = kd_height_weight();
+    const auto t0 = std::chrono::steady_clock::now();
+    DevBuf<int> maxb, head, hscan, bstart, cnt, cscan, lcnt, lscan, order2;
+    DevBuf<NwItem> segs;
+    int hmax[nwp::LEVELS];
+    NW_HIP(maxb.ensure(nwp::LEVELS));
+    NW_HIP(hipMemsetAsync(maxb.p, 0, sizeof(hmax), ctx->stream));
+    hipLaunchKernelGGL(k_kd_block_max, dim3(nblk(N)), dim3(NW_BLOCK), 0, ctx->stream, ctx->mkey.p, N, maxb.p);
+    NW_HIP(hipMemcpyAsync(hmax, maxb.p, sizeof(hmax), hipMemcpyDeviceToHost, ctx->stream));
+    NW_HIP(hipStreamSynchronize(ctx->stream));
+    const int level = nwp::start_level(hmax, cap);
+    NW_HIP(head.ensure(N)); NW_HIP(hscan.ensure((size_t)N + 1));
+    hipLaunchKernelGGL(k_block_heads, dim3(nblk(N)), dim3(NW_BLOCK), 0, ctx->stream, ctx->mkey.p, N, 3 * level, head.p);
+    NW_TRY(scan_exclusive(ctx, head.p, N, hscan.p));
+    int nblocks = 0, nsegs = 0, nleaves = 0;
+    NW_HIP(hipMemcpyAsync(&nblocks, hscan.p + N, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    NW_HIP(hipStreamSynchronize(ctx->stream));
+    NW_HIP(bstart.ensure((size_t)nblocks + 1));
+    hipLaunchKernelGGL(k_block_starts, dim3(nblk(N)), dim3(NW_BLOCK), 0, ctx->stream, head.p, hscan.p, N, bstart.p);
+    NW_HIP(cnt.ensure((size_t)nblocks)); NW_HIP(cscan.ensure((size_t)nblocks + 1));
+    hipLaunchKernelGGL(k_kd_seg_counts, dim3(nblk(nblocks)), dim3(NW_BLOCK), 0, ctx->stream, bstart.p, nblocks, cap, leaf, cnt.p);
+    NW_TRY(scan_exclusive(ctx, cnt.p, nblocks, cscan.p));
+    NW_HIP(hipMemcpyAsync(&nsegs, cscan.p + nblocks, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    NW_HIP(hipStreamSynchronize(ctx->stream));
+    NW_HIP(segs.ensure((size_t)nsegs));
+    hipLaunchKernelGGL(k_kd_fill_segs, dim3(nblk(nblocks)), dim3(NW_BLOCK), 0, ctx->stream, bstart.p, cscan.p, nblocks, cap, leaf, segs.p);
+    NW_HIP(lcnt.ensure((size_t)nsegs)); NW_HIP(lscan.ensure((size_t)nsegs + 1));
+    hipLaunchKernelGGL(k_kd_leaf_counts, dim3(nblk(nsegs)), dim3(NW_BLOCK), 0, ctx->stream, segs.p, nsegs, leaf, lcnt.p);
+    NW_TRY(scan_exclusive(ctx, lcnt.p, nsegs, lscan.p));
+    NW_HIP(hipMemcpyAsync(&nleaves, lscan.p + nsegs, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    NW_HIP(hipStreamSynchronize(ctx->stream));
+    NW_HIP(ctx->kd_leaves.ensure((size_t)nleaves));
+    hipLaunchKernelGGL(k_kd_fill_leaves, dim3(nblk(nsegs)), dim3(NW_BLOCK), 0, ctx->stream, segs.p, lscan.p, nsegs, leaf, ctx->kd_leaves.p);
+    NW_HIP(order2.ensure(N));
+    hipLaunchKernelGGL(k_kd_partition, dim3(nsegs), dim3(NWP_THREADS), 0, ctx->stream, segs.p, nsegs, order.p, ctx->proj_foot.p, ctx->face.p, leaf, w, order2.p);
+    NW_HIP(hipGetLastError());
+    NW_HIP(hipStreamSynchronize(ctx->stream));
+    if (getenv("NW_KD_KEEP")) {
+        // developer aid: what the partition was given, in the order it was given (the tests restate the partition from it)
+        std::vector<int> ord(N), face(N), perm(N);
+        std::vector<float> foot(4 * (size_t)N);
+        ctx->kd_dbg_key.resize(N); ctx->kd_dbg_foot.resize(4 * (size_t)N); ctx->kd_dbg_face.resize(N); ctx->kd_dbg_perm.resize(N);
+        NW_HIP(hipMemcpy(ord.data(), order.p, (size_t)N * sizeof(int), hipMemcpyDeviceToHost));
+        NW_HIP(hipMemcpy(face.data(), ctx->face.p, (size_t)N * sizeof(int), hipMemcpyDeviceToHost));
+        NW_HIP(hipMemcpy(perm.data(), ctx->perm.p, (size_t)N * sizeof(int), hipMemcpyDeviceToHost));
+        NW_HIP(hipMemcpy(foot.data(), ctx->proj_foot.p, 4 * (size_t)N * sizeof(float), hipMemcpyDeviceToHost));
+        NW_HIP(hipMemcpy(ctx->kd_dbg_key.data(), ctx->mkey.p, (size_t)N * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (int s = 0; s < N; ++s) {
+            const int o = ord[s];
+            ctx->kd_dbg_face[s] = face[o]; ctx->kd_dbg_perm[s] = perm[o];
+            for (int k = 0; k < 4; ++k) ctx->kd_dbg_foot[4 * (size_t)s + k] = foot[4 * (size_t)o + k];
+        }
+    }
+    if (getenv("NW_VERBOSE"))
+        fprintf(stderr, "[nanowrap] k-d partition: %d start segments at Morton level %d (largest block %d), %d leaves of %d, height weight %.2f: %ld us\n", nsegs, level,
+                hmax[level], nleaves, leaf, w, (long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count());
+    order.swap(order2);
+    ctx->kd_nleaves = nleaves; ctx->kd_leaf = leaf; ctx->kd_nsegs = nsegs; ctx->kd_level = level;
+    return NW_OK;
+}
+
 static int resort_by_projection(nw_ctx *ctx)
 {
     const int64_t N = ctx->N;
@@ -1244,6 +1359,7 @@ static int resort_by_projection(nw_ctx *ctx)
     if (ctx->w_array) NW_HIP(wnorm2.ensure(3 * N));
     const int se = nw_sort_pairs_u32(ctx->proj_key.p, ctx->mkey.p, ctx->proj_idx.p, order.p, (int)N, 30, ctx->stream);
     if (se != 0) return fail(ctx, NW_ERR_HIP, std::string("radix sort of the projection keys: ") + hipGetErrorString((hipError_t)se));
+    if (kd_sort_on()) NW_TRY(kd_partition(ctx, order));
     hipLaunchKernelGGL(k_point_regather, dim3(nblk(N)), dim3(NW_BLOCK), 0, ctx->stream, (int)N, order.p, ctx->pts.p, ctx->perm.p,
                        ctx->sinv_array ? ctx->sinv.p : nullptr, ctx->w_array ? ctx->wnorm.p : nullptr, ctx->mask.p, ctx->face.p,
                        pts2.p, perm2.p, sinv2.p, wnorm2.p, mask2.p, face2.p);
@@ -1257,7 +1373,7 @@ static int resort_by_projection(nw_ctx *ctx)
     ctx->grid_valid = false;                 // the work list is cut again (build_grid)
     ctx->proj_sorted = true; ctx->proj_ready = false;
     ctx->searched = false;                   // cached per-localization results are in the old order
-    ctx->proj_key.release(); ctx->proj_idx.release();
+    ctx->proj_key.release(); ctx->proj_idx.release(); ctx->proj_foot.release();
     if (ctx->have_data) NW_TRY(gather_data(ctx));
     if (getenv("NW_VERBOSE")) fprintf(stderr, "[nanowrap] localizations re-sorted by their foot point on the surface\n");
     return NW_OK;
@@ -1832,8 +1948,10 @@ NW_EXPORT int nw_search_end(nw_ctx *ctx, float *pos_out, nw_iter_log *log, int *
         const double ext = std::max({(double)g.gx, (double)g.gy, (double)g.gz}) * g.h;
         ctx->proj_unit = (float)(ext / 1024.0);
         NW_HIP(ctx->proj_key.ensure(ctx->N)); NW_HIP(ctx->proj_idx.ensure(ctx->N));
+        const bool kd = kd_sort_on() && !getenv("NW_NO_PROJ_SORT");
+        if (kd) NW_HIP(ctx->proj_foot.ensure(ctx->N));
         hipLaunchKernelGGL(k_projection_keys, dim3(nblk(ctx->N)), dim3(NW_BLOCK), 0, ctx->stream, (int)ctx->N, ctx->face.p, (int)ctx->F, ctx->cent_tmp.p, ctx->pts.p,
-                           g.ox, g.oy, g.oz, 1.0f / ctx->proj_unit, ctx->proj_key.p, ctx->proj_idx.p);
+                           g.ox, g.oy, g.oz, 1.0f / ctx->proj_unit, ctx->proj_key.p, ctx->proj_idx.p, ctx->pos.p, ctx->faces.p, kd ? ctx->proj_foot.p : (float4 *)nullptr);
         NW_HIP(hipGetLastError());
         NW_HIP(hipStreamSynchronize(ctx->stream));
         ctx->proj_ready = true;
@@ -2622,6 +2740,29 @@ NW_EXPORT int nw_debug(nw_ctx *ctx, int what, void *a, void *b, int cap, int *n)
     if (what == 3 && ctx) {               // cap != 0: the attraction step as a launch of its own from now on (per-stage timings); 0: back inside the query launch
         if (ctx->in_search) return fail(ctx, NW_ERR_BADARG, "nw_debug(3) inside a search");
         ctx->handoff_off = cap != 0;
+        return NW_OK;
+    }
+    if (what == 4 && ctx && a && n) {
+        // the layout: sorted slot -> the caller's index (a = int32[cap], *n = localizations); b (optional) = int32[5]: the k-d work list of
+        // the second sort {leaves, start segments, their Morton level, localizations per leaf, the height weight's float bits}, zeros before it
+        *n = (int)ctx->N;
+        if (b) {
+            int32_t *kd = (int32_t *)b;
+            const float w = kd_height_weight();
+            kd[0] = ctx->kd_nleaves; kd[1] = ctx->kd_nleaves > 0 ? ctx->kd_nsegs : 0; kd[2] = ctx->kd_nleaves > 0 ? ctx->kd_level : 0;
+            kd[3] = ctx->kd_nleaves > 0 ? ctx->kd_leaf : 0;
+            memcpy(&kd[4], &w, 4);
+        }
+        if (ctx->perm.p && cap > 0) NW_HIP(hipMemcpy(a, ctx->perm.p, (size_t)std::min<int64_t>(cap, ctx->N) * sizeof(int), hipMemcpyDeviceToHost));
+        return NW_OK;
+    }
+    if ((what == 5 || what == 6) && ctx && a && b && n) {
+        // with NW_KD_KEEP set: what the k-d partition of the second sort was given, in the order of its sorted keys.  what = 5: a = uint32
+        // key[cap], b = float (foot x, y, z, signed height)[4 cap]; what = 6: a = int32 nearest face[cap], b = int32 the caller's index[cap]
+        const size_t have = ctx->kd_dbg_key.size(), m = std::min<size_t>((size_t)std::max(cap, 0), have);
+        *n = (int)have;
+        if (what == 5) { memcpy(a, ctx->kd_dbg_key.data(), m * sizeof(uint32_t)); memcpy(b, ctx->kd_dbg_foot.data(), 4 * m * sizeof(float)); }
+        else { memcpy(a, ctx->kd_dbg_face.data(), m * sizeof(int)); memcpy(b, ctx->kd_dbg_perm.data(), m * sizeof(int)); }
         return NW_OK;
     }
     return NW_ERR_BADARG;

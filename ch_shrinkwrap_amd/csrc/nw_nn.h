@@ -158,13 +158,31 @@ __global__ void k_point_gather(int N, const float *__restrict__ xyz, const int *
 // localization's nearest face, i.e. of its foot point on the surface.  Localizations over the same patch of surface become
 // neighbours in the list whatever their height above it, so a wave's 64 localizations share one small set of candidate cells
 // (in the plain 3-D Morton order a wave's box is as wide as its localizations are scattered in height).  Speed only.
+// foot (optional): the foot point and the signed height (p - centroid) . n of the localization over that face, n the unit normal of the
+// face's three current vertices -- the four coordinates of the k-d work list (nw_partition_core.h).  Height 0 where there is no face or
+// anything is non-finite.
 __global__ void k_projection_keys(int N, const int *__restrict__ face, int F, const float4 *__restrict__ cent_by_face, const float4 *__restrict__ pts,
-                                  float lox, float loy, float loz, float inv_unit, unsigned *__restrict__ key, int *__restrict__ idx)
+                                  float lox, float loy, float loz, float inv_unit, unsigned *__restrict__ key, int *__restrict__ idx,
+                                  const float *__restrict__ pos, const int *__restrict__ faces, float4 *__restrict__ foot)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
     const int f = face[i];
     const float4 C = ((unsigned)f < (unsigned)F) ? cent_by_face[f] : pts[i];
+    if (foot) {
+        float h = 0.0f;
+        if ((unsigned)f < (unsigned)F) {
+            const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
+            const float ax = pos[3 * a], ay = pos[3 * a + 1], az = pos[3 * a + 2];
+            const float ux = pos[3 * b] - ax, uy = pos[3 * b + 1] - ay, uz = pos[3 * b + 2] - az;
+            const float vx = pos[3 * c] - ax, vy = pos[3 * c + 1] - ay, vz = pos[3 * c + 2] - az;
+            const float nx = uy * vz - uz * vy, ny = uz * vx - ux * vz, nz = ux * vy - uy * vx;
+            const float4 P = pts[i];
+            h = ((P.x - C.x) * nx + (P.y - C.y) * ny + (P.z - C.z) * nz) * rsqrtf(nx * nx + ny * ny + nz * nz);
+            if (!isfinite(h)) h = 0.0f;
+        }
+        foot[i] = make_float4(C.x, C.y, C.z, h);
+    }
     const int qx = nw_clampi((int)((C.x - lox) * inv_unit), 0, 1023);
     const int qy = nw_clampi((int)((C.y - loy) * inv_unit), 0, 1023);
     const int qz = nw_clampi((int)((C.z - loz) * inv_unit), 0, 1023);

@@ -349,7 +349,14 @@ int nw_accumulator_quantum(nw_ctx *ctx, double *q);
  *   the device-side stop condition ended early) -- a block must take ONE of the two.
  * what = 3: cap != 0 makes the attraction step a launch of its own from now on (k_attract behind the query), cap = 0 puts it back into the
  *   query launch (workgroups appended to k_nn_wave's grid: the default).  Results are bit-identical either way; bench.py takes its per-stage
- *   timings with the steps apart. */
+ *   timings with the steps apart.
+ * what = 4: the layout of the localizations -- a = int32 perm[cap]: sorted slot -> the caller's index, *n = localizations; b (optional) =
+ *   int32[5]: the k-d work list cut by the second sort {leaves, start segments, their Morton level, localizations per leaf, the float bits
+ *   of the height weight}; leaves = 0 before that sort, with NW_KD_SORT=0 and with NW_NO_PROJ_SORT.
+ * what = 5, 6: with NW_KD_KEEP set in the environment when the second sort runs, what its k-d partition was given, in the order of the
+ *   sorted foot-point keys (the tests restate the partition from it: csrc/nw_partition_core.h).  5: a = uint32 key[cap], b = float
+ *   {foot x, y, z, signed height}[cap]; 6: a = int32 nearest face (the library's own id)[cap], b = int32 the caller's index[cap];
+ *   *n = localizations kept (0: nothing). */
 int nw_debug(nw_ctx *ctx, int what, void *a, void *b, int cap, int *n);
 
 /* ---- the block-boundary remesher on the device (ABI 6) ---------------------------------------------------------------------------
