@@ -44,6 +44,7 @@ OBJ_VOLUME = _csrc('nw_volume.o')
 OBJ_PROXIMITY = _csrc('nw_proximity.o')
 OBJ_MAPPING = _csrc('nw_mapping.o')
 OBJ_CLUSTERING = _csrc('nw_clustering.o')
+OBJ_PAIRS = _csrc('nw_pairs.o')
 # the translation units of libnanowrap_hip.so: (source, object, what else it is rebuilt for, flags).  The objects are linked in this order.
 UNITS = [
     # the per-iteration kernels and the C-ABI; every header of csrc/ but nw_bq.h and nw_bq_core.h is included by it (directly or through
@@ -100,6 +101,10 @@ UNITS = [
     # the squared distance and the ring bound)
     (_csrc('nw_clustering.hip'), OBJ_CLUSTERING, [_include('nw_clustering.h'), _csrc('nw_clustering_core.h'), _csrc('nw_neighbours_core.h')] + _BQ_H,
      _QUERY),
+    # pair-distance counts of the cloud: the histogram of pair distances and the same counts per localization (nw_pairs_core.h: the
+    # edges, the bin and the walk over a clamped box of cells, which the tests also compile for the CPU; it includes
+    # nw_neighbours_core.h for the squared distance and the cell slack)
+    (_csrc('nw_pairs.hip'), OBJ_PAIRS, [_include('nw_pairs.h'), _csrc('nw_pairs_core.h'), _csrc('nw_neighbours_core.h')] + _BQ_H, _QUERY),
 ]
 DEPS = sorted(set(d for src, _, extra, _ in UNITS for d in [src] + extra))
 
@@ -260,6 +265,11 @@ KERNEL_BUDGETS = {
     'k_pc_border':                    (56, 64),            # the same walk and the best (d2, index): 8 waves per SIMD
     'k_pc_stats':                     (40, 96),            # eight values through the wave's butterflies: 8 waves per SIMD; LDS = the four waves' three counters
     'k_pc_totals':                    (64, 256),           # eight 64-bit sums per thread, one workgroup: 8 waves per SIMD; LDS = the four waves' eight counters
+    # pair-distance counts (csrc/nw_pairs.o): one lane per query, its counters in a column of LDS, no atomics on the results; zero scratch
+    'k_pq_order':                     (16, 0),
+    'k_pq_pairs<false>':              (56, 8 * 1024),      # up to 16 bins: 128 lanes x 16 bins x 4 bytes; the edges are scalar operands
+    'k_pq_pairs<true>':               (56, 17 * 1024),     # up to 64 bins: 64 lanes x 64 bins x 4 bytes and the LDS copy of the edges (512 bytes)
+    'k_pq_totals':                    (24, 2048),          # LDS = one 64-bit sum per thread
     # what the eleven units above share (csrc/nw_bq.o), and nw_mapping.o: the exclusive scan, and the point grid of hole punching (f32) and of the metric (f64)
     'k_bq_scan_tiles':                (32, 1024),
     'k_bq_scan_bsums':                (32, 1024),
@@ -271,7 +281,7 @@ KERNEL_BUDGETS = {
     'k_bq_cell_count_f64':            (48, 0),
     'k_bq_scatter_f64':               (16, 0),
 }
-BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_DISTANCE, OBJ_NEIGHBOURS, OBJ_INTERSECTIONS, OBJ_RAYS, OBJ_VOLUME, OBJ_PROXIMITY, OBJ_MAPPING, OBJ_CLUSTERING, OBJ_BQ]
+BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_DISTANCE, OBJ_NEIGHBOURS, OBJ_INTERSECTIONS, OBJ_RAYS, OBJ_VOLUME, OBJ_PROXIMITY, OBJ_MAPPING, OBJ_CLUSTERING, OBJ_PAIRS, OBJ_BQ]
 
 
 def kernel_resources(obj=None):

@@ -1,0 +1,383 @@
+// Exact pair-distance counts of a localization cloud on the device (MI355X, gfx950): include/nw_pairs.h.
+//
+//   (bq::bounds, bq::size_grid, bq::build_grid)   the query units' shared point grid in float: bounding box and finiteness of the cloud,
+//                                     cell of every point and the cells' starts
+//   k_pq_order       the cloud in cell order with every point's index in the caller's array (the shared scatter keeps coordinates only)
+//   k_pq_pairs<W>    one lane per query (auto mode: the cloud's points in cell order; cross mode: the caller's order): the walk of
+//                    nwq_walk, every visited point's bin, the lane's m counters in a column of LDS ([bin][lane], uint32: the column
+//                    stride is the workgroup's size, so a wave's increments never share a bank whatever their bins are, and nothing
+//                    is indexed at run time in registers); no atomics.  At the end the column goes to `local` if asked, and the
+//                    workgroup's columns are added per bin into one row of 64-bit partial sums
+//   k_pq_totals      the partial rows, one workgroup; integer sums: any order gives the same bits
+//
+// Two instantiations of one template.  <false>, up to 16 bins: 128 lanes, 16 x 128 x 4 bytes = 8 KB of LDS; the edges are kernel
+// arguments, padded with +inf to 16, and the bin is the definition itself -- a sum of 16 comparisons against scalar operands, without a
+// branch.  <true>, up to 64 bins: the bin is nwq_bin_search over an LDS copy of the padded edges.  64 bins x 128 lanes x 4 bytes are
+// 32 KB on their own and would leave no room for that copy, so this variant runs 64 lanes a workgroup: 16 KB of columns and 512 bytes of
+// edges.  With either size the LDS lets the same number of waves onto a CU.
+//
+// The definition -- the edges, the bin, the walk with its proof -- is csrc/nw_pairs_core.h, which the tests also compile for the CPU.
+// The device buffer, the point grid and the context's scaffolding are the query units' shared ones (nw_bq.h).
+// All stores are vector stores; no kernel uses scratch (build.py's KERNEL_BUDGETS checks it).
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include <cstdlib>
+#include <cmath>
+#include <string>
+#include <algorithm>
+
+#include "../../include/nw_pairs.h"
+#include "nw_bq.h"
+#include "nw_pairs_core.h"
+
+#define NWQ_EXPORT extern "C" __attribute__((visibility("default")))
+#define NWQ_BLOCK 256               // k_pq_order, k_pq_totals
+#define NWQ_LANES_NARROW 128
+#define NWQ_LANES_WIDE 64
+// a workgroup's two counters beside its row of bins
+#define NWQ_COUNTERS 2
+#define NWQ_C_TESTS 0
+#define NWQ_C_CELLS 1
+
+typedef unsigned long long u64;
+typedef unsigned int u32;
+
+// the edges of the narrow variant: kernel arguments, so uniform operands
+struct pq_edges {
+    double e2[NWQ_NARROW_BINS];
+};
+
+__global__ __launch_bounds__(NWQ_BLOCK) void k_pq_order(const float *__restrict__ xyz, int n, const int *__restrict__ cell, int *__restrict__ cursor,
+                                                        nwq_pt *__restrict__ pts)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int slot = atomicAdd(&cursor[cell[i]], 1);          // (order inside a cell is arbitrary: no output depends on it)
+    if (slot < 0 || slot >= n) return;                        // (cannot happen: the cursors start at the scan of the counts)
+    nwq_pt p;
+    p.x = xyz[3 * (int64_t)i]; p.y = xyz[3 * (int64_t)i + 1]; p.z = xyz[3 * (int64_t)i + 2]; p.i = i;
+    pts[slot] = p;
+}
+
+// what a lane does with a visited point: its bin, one increment in the lane's column
+template <bool WIDE> struct pq_visit {
+    double x, y, z;
+    int self;                           // the index that is not a pair with the query (-1: none)
+    int m;
+    const double *e2;                   // WIDE: the LDS copy of the padded edges
+    pq_edges E;                         // else: the padded edges as uniform operands
+    u32 *col;                           // the lane's column: bin b at col[b * lanes]
+    u32 tests;
+    __device__ __forceinline__ void operator()(const nwq_pt &p)
+    {
+        if (p.i == self) return;
+        ++tests;
+        const double d2 = nwq_dist2(p, x, y, z);
+        int bin;
+        if (WIDE) {
+            bin = nwq_bin_search(e2, d2);
+        } else {
+            bin = 0;
+#pragma unroll
+            for (int b = 0; b < NWQ_NARROW_BINS; ++b) bin += E.e2[b] < d2 ? 1 : 0;
+        }
+        if (bin < m) col[bin * (WIDE ? NWQ_LANES_WIDE : NWQ_LANES_NARROW)] += 1u;
+    }
+};
+
+// queries = nullptr: auto mode, lane p is the cloud's p-th point in cell order and leaves itself out by index
+template <bool WIDE>
+__global__ __launch_bounds__(WIDE ? NWQ_LANES_WIDE : NWQ_LANES_NARROW) void k_pq_pairs(const float *__restrict__ queries, int nq, const nwq_pt *__restrict__ pts,
+                                                                                      const int *__restrict__ cstart, nwq_grid G, pq_edges E,
+                                                                                      const double *__restrict__ e2_all, int m, double r_max, double r_max2,
+                                                                                      u32 *__restrict__ local, u64 *__restrict__ part_hist,
+                                                                                      u64 *__restrict__ part_cnt, int *__restrict__ bad /* bit 0: a non-finite query */)
+{
+    constexpr int LANES = WIDE ? NWQ_LANES_WIDE : NWQ_LANES_NARROW;
+    constexpr int BINS = WIDE ? NWQ_MAX_BINS : NWQ_NARROW_BINS;
+    constexpr int WAVES = LANES / 64;
+    // the columns, and behind them the wide variant's copy of the edges (64 doubles)
+    __shared__ alignas(16) u32 s_col[BINS * LANES + (WIDE ? 2 * NWQ_MAX_BINS : 0)];
+    double *s_e2 = (double *)(s_col + BINS * LANES);
+    const int lane = threadIdx.x;
+    const int p = blockIdx.x * LANES + lane;
+    if (WIDE && lane < NWQ_MAX_BINS) s_e2[lane] = e2_all[lane];
+#pragma unroll
+    for (int b = 0; b < BINS; ++b) s_col[b * LANES + lane] = 0u;
+    __syncthreads();
+
+    u64 tests = 0, cells = 0;
+    int64_t row = -1;                                         // where the lane's counts go in `local`
+    if (p < nq) {
+        pq_visit<WIDE> v;
+        bool ok = true;
+        if (queries) {
+            const float fx = queries[3 * (int64_t)p], fy = queries[3 * (int64_t)p + 1], fz = queries[3 * (int64_t)p + 2];
+            ok = isfinite(fx) && isfinite(fy) && isfinite(fz);
+            if (!ok) atomicOr(bad, 1);
+            v.x = (double)fx; v.y = (double)fy; v.z = (double)fz;
+            v.self = -1;
+            row = p;
+        } else {
+            const nwq_pt pt = pts[p];
+            v.x = (double)pt.x; v.y = (double)pt.y; v.z = (double)pt.z;
+            v.self = pt.i;
+            row = pt.i;
+        }
+        if (ok) {
+            v.m = m;
+            v.e2 = s_e2;
+            v.E = E;
+            v.col = s_col + lane;
+            v.tests = 0u;
+            long long read = 0;
+            nwq_walk(pts, cstart, G, v.x, v.y, v.z, r_max, r_max2, v, &read);
+            tests = v.tests;
+            cells = (u64)read;
+        }
+    }
+    if (local && row >= 0) {
+        for (int b = 0; b < m; ++b) local[row * m + b] = s_col[b * LANES + lane];
+    }
+    __syncthreads();
+    // thread b adds row b over the lanes, starting b lanes in: the threads of a wave read different banks
+    u64 sum = 0;
+    if (lane < m) {
+        for (int j = 0; j < LANES; ++j) sum += s_col[lane * LANES + ((j + lane) & (LANES - 1))];
+    }
+    if (lane < BINS) part_hist[(int64_t)blockIdx.x * BINS + lane] = sum;
+    // the two counters: a butterfly within each wave, then the waves through the columns' memory
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { tests += __shfl_xor(tests, o, 64); cells += __shfl_xor(cells, o, 64); }
+    __syncthreads();                                          // (the columns have been read)
+    u64 *s_w = (u64 *)s_col;
+    if ((lane & 63) == 0) { s_w[(lane >> 6) * NWQ_COUNTERS + NWQ_C_TESTS] = tests; s_w[(lane >> 6) * NWQ_COUNTERS + NWQ_C_CELLS] = cells; }
+    __syncthreads();
+    if (lane < NWQ_COUNTERS) {
+        u64 s = 0;
+        for (int w = 0; w < WAVES; ++w) s += s_w[w * NWQ_COUNTERS + lane];
+        part_cnt[(int64_t)blockIdx.x * NWQ_COUNTERS + lane] = s;
+    }
+}
+
+// out[c] = the sum of column c of rows[nb][width], width a power of two up to NWQ_BLOCK: a thread adds every (NWQ_BLOCK / width)-th row
+// of its column, then the column's threads are added in order
+__device__ __forceinline__ void pq_column_sums(const u64 *__restrict__ rows, int64_t nb, int width, u64 *__restrict__ out, u64 *s_acc)
+{
+    const int c = threadIdx.x & (width - 1), s = threadIdx.x / width, slices = NWQ_BLOCK / width;
+    u64 acc = 0;
+    for (int64_t b = s; b < nb; b += slices) acc += rows[b * width + c];
+    __syncthreads();
+    s_acc[threadIdx.x] = acc;
+    __syncthreads();
+    if (threadIdx.x < width) {
+        u64 t = 0;
+        for (int k = 0; k < slices; ++k) t += s_acc[k * width + threadIdx.x];
+        out[threadIdx.x] = t;
+    }
+}
+
+// totals[0 .. bins) = hist (the rows' padding adds zeros), totals[NWQ_MAX_BINS ..] = the two counters
+__global__ __launch_bounds__(NWQ_BLOCK) void k_pq_totals(const u64 *__restrict__ part_hist, const u64 *__restrict__ part_cnt, int64_t nb, int bins,
+                                                         u64 *__restrict__ totals)
+{
+    __shared__ u64 s_acc[NWQ_BLOCK];
+    pq_column_sums(part_hist, nb, bins, totals, s_acc);
+    pq_column_sums(part_cnt, nb, NWQ_COUNTERS, totals + NWQ_MAX_BINS, s_acc);
+}
+
+// =====================================================================================================================================
+// host side
+// =====================================================================================================================================
+using bq::DevBuf;
+using bq::fail;
+
+struct nwq_ctx : bq::Ctx {
+    // the cloud (nwq_set_cloud) and its box
+    int n = 0;
+    DevBuf cloud, mm;
+    bq::Grid<float> g{};
+    double h_start = 0.0;               // the cell size the grid at hand was sized from (0: none)
+    DevBuf cell, cursor, cstart, sorted, scan_tmp, pts;
+    // the edges (nwq_set_edges): m = 0 until then
+    int m = 0;
+    double radii[NWQ_MAX_BINS], e2[NWQ_MAX_BINS];
+    bool edges_on_device = false;
+    DevBuf e2_dev;
+    double cell_of_rmax = NWQ_CELL_OF_RMAX;
+    // one count
+    DevBuf q, local, part_hist, part_cnt, totals, flag;
+};
+
+namespace {
+
+#define NWQ_HIP(call) BQ_HIP(call, NWQ_ERR_NOMEM, NWQ_ERR_HIP)
+
+// at most max(2 n, 65536) cells, up to 2^26; at most 1025 an axis (NWK_CELL_SLACK rests on it); 400 widening steps
+const bq::GridRule NWQ_GRID_RULE = {2, 1ll << 26, 1025, 400};
+
+// the cell size a count starts from: NWQ_CELL_OF_RMAX of the largest radius, never below 1/1024 of the widest axis (the walk's proof
+// needs it); a cloud without extent and a zero radius get one cell of side 1
+double starting_cell(const nwq_ctx *ctx, double r_max)
+{
+    double emax = 0.0;
+    for (int d = 0; d < 3; ++d) emax = std::max(emax, (double)ctx->g.hi[d] - (double)ctx->g.lo[d]);
+    double h = std::max(ctx->cell_of_rmax * r_max, emax / 1024.0);
+    if (!((float)h > 0.0f) || !std::isfinite((float)h)) h = (emax > 0.0 && std::isfinite((float)emax)) ? emax : 1.0;
+    return h;
+}
+
+// the grid for edges with this largest radius: the one at hand if it was sized from the same starting cell, else the cloud binned anew
+int ensure_grid(nwq_ctx *ctx, double r_max)
+{
+    const double h0 = starting_cell(ctx, r_max);
+    if (ctx->h_start == h0) return NWQ_OK;
+    ctx->h_start = 0.0;
+    double ext[3];
+    for (int d = 0; d < 3; ++d) ext[d] = (double)ctx->g.hi[d] - (double)ctx->g.lo[d];
+    double h = h0;
+    if (!bq::size_grid(NWQ_GRID_RULE, ctx->n, ext, &h, ctx->g.dims)) return fail(ctx, NWQ_ERR_BADARG, "nwq: no cell size keeps the grid within its cap");
+    ctx->g.h = (float)h;
+    if (!(ctx->g.h > 0.0f) || !std::isfinite(ctx->g.h)) return fail(ctx, NWQ_ERR_BADARG, "nwq: the cell size is not a positive float");
+    int total = -1;
+    NWQ_HIP(bq::build_grid<float>(ctx->stream, ctx->cloud.as<float>(), ctx->n, ctx->g, ctx->cell, ctx->cursor, ctx->scan_tmp, ctx->cstart, ctx->sorted, &total));
+    if (total != ctx->n) return fail(ctx, NWQ_ERR_HIP, "nwq: the cell counts do not add up to the cloud");
+    // the same order once more, with the indices
+    NWQ_HIP(ctx->pts.ensure(sizeof(nwq_pt) * (size_t)ctx->n));
+    NWQ_HIP(hipMemcpyAsync(ctx->cursor.p, ctx->cstart.p, sizeof(int) * (size_t)ctx->g.cells(), hipMemcpyDeviceToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_pq_order, dim3(bq::nblk(ctx->n, NWQ_BLOCK)), dim3(NWQ_BLOCK), 0, ctx->stream, ctx->cloud.as<float>(), ctx->n, ctx->cell.as<int>(),
+                       ctx->cursor.as<int>(), ctx->pts.as<nwq_pt>());
+    NWQ_HIP(hipGetLastError());
+    NWQ_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->h_start = h0;
+    return NWQ_OK;
+}
+
+}  // namespace
+
+NWQ_EXPORT int nwq_abi_version(void) { return NWQ_ABI_VERSION; }
+
+NWQ_EXPORT int nwq_create(int device, nwq_ctx **out)
+{
+    const int r = bq::create(device, out, NWQ_ERR_BADARG, NWQ_ERR_HIP);
+    if (r != 0) return r;
+    // (developer knob for profiles/pairs.txt's sweep of the starting cell; no output depends on it)
+    const char *s = std::getenv("NW_PAIRS_CELL_OF_RMAX");
+    const double v = s ? std::atof(s) : 0.0;
+    if (v >= 0.01 && v <= 100.0) (*out)->cell_of_rmax = v;
+    return NWQ_OK;
+}
+
+NWQ_EXPORT void nwq_destroy(nwq_ctx *ctx) { bq::destroy(ctx); }
+
+NWQ_EXPORT const char *nwq_last_error(nwq_ctx *ctx) { return bq::last_error(ctx); }
+
+NWQ_EXPORT int nwq_set_cloud(nwq_ctx *ctx, const float *xyz, int64_t n, int on_device)
+{
+    if (!xyz || n < 1 || n > NWQ_MAX_N || (on_device != 0 && on_device != 1)) return NWQ_ERR_BADARG;
+    if (!on_device && !bq::all_finite(xyz, 3 * n)) {
+        if (ctx) { ctx->n = 0; ctx->h_start = 0.0; }              // (a failed call leaves no cloud, whichever check failed)
+        return fail(ctx, NWQ_ERR_NONFINITE, "nwq_set_cloud: a localization is not finite");
+    }
+    if (!ctx) return NWQ_ERR_BADARG;
+    NWQ_HIP(hipSetDevice(ctx->device));
+    ctx->n = 0;
+    ctx->h_start = 0.0;
+    NWQ_HIP(ctx->cloud.ensure(sizeof(float) * 3 * (size_t)n));
+    NWQ_HIP(hipMemcpyAsync(ctx->cloud.p, xyz, sizeof(float) * 3 * (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    bool finite[2];
+    NWQ_HIP(bq::bounds<float>(ctx->stream, ctx->mm, ctx->cloud.as<float>(), (int)n, nullptr, 0, &ctx->g, finite));
+    if (!finite[0]) return fail(ctx, NWQ_ERR_NONFINITE, "nwq_set_cloud: a localization is not finite");
+    ctx->n = (int)n;
+    return NWQ_OK;
+}
+
+NWQ_EXPORT int nwq_set_edges(nwq_ctx *ctx, const double *radii, int64_t m)
+{
+    double e2[NWQ_MAX_BINS];
+    if (!nwq_edges(radii, m, e2)) return fail(ctx, NWQ_ERR_BADARG, "nwq_set_edges: 1 to 64 finite radii, 0 <= r_0 < r_1 < ... <= 2^40, with ascending squares");
+    if (!ctx) return NWQ_ERR_BADARG;
+    ctx->m = (int)m;
+    for (int b = 0; b < NWQ_MAX_BINS; ++b) { ctx->e2[b] = e2[b]; ctx->radii[b] = b < m ? radii[b] : 0.0; }
+    ctx->edges_on_device = false;
+    return NWQ_OK;
+}
+
+NWQ_EXPORT int nwq_count(nwq_ctx *ctx, const float *queries, int64_t nq, int on_device, uint64_t *hist, uint32_t *local, int64_t *info)
+{
+    if (!hist || !info || (on_device != 0 && on_device != 1)) return NWQ_ERR_BADARG;
+    if (queries ? (nq < 1 || nq > NWQ_MAX_N) : nq < 0) return NWQ_ERR_BADARG;
+    if (queries && !on_device && !bq::all_finite(queries, 3 * nq)) return fail(ctx, NWQ_ERR_NONFINITE, "nwq_count: a query is not finite");
+    if (!ctx) return NWQ_ERR_BADARG;
+    if (ctx->n < 1) return fail(ctx, NWQ_ERR_NOCLOUD, "nwq_count: nwq_set_cloud first");
+    if (ctx->m < 1) return fail(ctx, NWQ_ERR_NOCLOUD, "nwq_count: nwq_set_edges first");
+    if (!queries && nq != 0 && nq != ctx->n) return fail(ctx, NWQ_ERR_BADARG, "nwq_count: without queries nq is 0 or the cloud's n");
+    NWQ_HIP(hipSetDevice(ctx->device));
+    const int m = ctx->m;
+    const double r_max = ctx->radii[m - 1], r_max2 = ctx->e2[m - 1];
+    const int r = ensure_grid(ctx, r_max);
+    if (r != NWQ_OK) return r;
+    hipStream_t st = ctx->stream;
+    const int n_queries = queries ? (int)nq : ctx->n;
+    const bool wide = m > NWQ_NARROW_BINS;
+    const int lanes = wide ? NWQ_LANES_WIDE : NWQ_LANES_NARROW, bins = wide ? NWQ_MAX_BINS : NWQ_NARROW_BINS;
+    const int nb = bq::nblk(n_queries, lanes);
+
+    const float *dq = nullptr;
+    if (queries) {
+        dq = queries;
+        if (!on_device) {
+            NWQ_HIP(bq::upload(st, ctx->q, queries, 3 * nq));
+            dq = ctx->q.as<float>();
+        }
+    }
+    if (!ctx->edges_on_device) {
+        NWQ_HIP(bq::upload(st, ctx->e2_dev, ctx->e2, NWQ_MAX_BINS));
+        NWQ_HIP(hipStreamSynchronize(st));
+        ctx->edges_on_device = true;
+    }
+    const size_t local_words = (size_t)n_queries * (size_t)m;
+    if (local)
+        NWQ_HIP(ctx->local.ensure(sizeof(u32) * local_words));
+    NWQ_HIP(ctx->part_hist.ensure(sizeof(u64) * (size_t)bins * (size_t)nb));
+    NWQ_HIP(ctx->part_cnt.ensure(sizeof(u64) * NWQ_COUNTERS * (size_t)nb));
+    NWQ_HIP(ctx->totals.ensure(sizeof(u64) * (NWQ_MAX_BINS + NWQ_COUNTERS)));
+    NWQ_HIP(ctx->flag.ensure(sizeof(int)));
+    NWQ_HIP(hipMemsetAsync(ctx->flag.p, 0, sizeof(int), st));
+
+    nwq_grid G;
+    for (int d = 0; d < 3; ++d) { G.lo[d] = (double)ctx->g.lo[d]; G.hi[d] = (double)ctx->g.hi[d]; G.dims[d] = ctx->g.dims[d]; }
+    G.h = (double)ctx->g.h;
+    pq_edges E;
+    for (int b = 0; b < NWQ_NARROW_BINS; ++b) E.e2[b] = ctx->e2[b];
+    u32 *dlocal = local ? ctx->local.as<u32>() : nullptr;
+    if (wide)
+        hipLaunchKernelGGL(k_pq_pairs<true>, dim3(nb), dim3(lanes), 0, st, dq, n_queries, ctx->pts.as<nwq_pt>(), ctx->cstart.as<int>(), G, E, ctx->e2_dev.as<double>(),
+                           m, r_max, r_max2, dlocal, ctx->part_hist.as<u64>(), ctx->part_cnt.as<u64>(), ctx->flag.as<int>());
+    else
+        hipLaunchKernelGGL(k_pq_pairs<false>, dim3(nb), dim3(lanes), 0, st, dq, n_queries, ctx->pts.as<nwq_pt>(), ctx->cstart.as<int>(), G, E, ctx->e2_dev.as<double>(),
+                           m, r_max, r_max2, dlocal, ctx->part_hist.as<u64>(), ctx->part_cnt.as<u64>(), ctx->flag.as<int>());
+    hipLaunchKernelGGL(k_pq_totals, dim3(1), dim3(NWQ_BLOCK), 0, st, ctx->part_hist.as<u64>(), ctx->part_cnt.as<u64>(), (int64_t)nb, bins, ctx->totals.as<u64>());
+    NWQ_HIP(hipGetLastError());
+
+    u64 tot[NWQ_MAX_BINS + NWQ_COUNTERS];
+    int bad = 0;
+    NWQ_HIP(hipMemcpyAsync(tot, ctx->totals.p, sizeof(tot), hipMemcpyDeviceToHost, st));
+    NWQ_HIP(hipMemcpyAsync(&bad, ctx->flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    NWQ_HIP(hipStreamSynchronize(st));
+    if (bad) return fail(ctx, NWQ_ERR_NONFINITE, "nwq_count: a query is not finite");
+    if (local) {
+        NWQ_HIP(hipMemcpyAsync(local, ctx->local.p, sizeof(u32) * local_words, hipMemcpyDeviceToHost, st));
+        NWQ_HIP(hipStreamSynchronize(st));
+    }
+    for (int b = 0; b < m; ++b) hist[b] = tot[b];
+    info[NWQ_INFO_TESTS] = (int64_t)tot[NWQ_MAX_BINS + NWQ_C_TESTS];
+    info[NWQ_INFO_CELLS_READ] = (int64_t)tot[NWQ_MAX_BINS + NWQ_C_CELLS];
+    info[NWQ_INFO_CELL_SIZE] = __builtin_bit_cast(int64_t, G.h);
+    info[NWQ_INFO_CELLS] = ctx->g.cells();
+    info[NWQ_INFO_VARIANT] = wide ? 1 : 0;
+    info[NWQ_INFO_N_QUERIES] = n_queries;
+    info[NWQ_INFO_N_CLOUD] = ctx->n;
+    info[NWQ_INFO_BINS] = m;
+    return NWQ_OK;
+}
