@@ -45,6 +45,7 @@ OBJ_PROXIMITY = _csrc('nw_proximity.o')
 OBJ_MAPPING = _csrc('nw_mapping.o')
 OBJ_CLUSTERING = _csrc('nw_clustering.o')
 OBJ_PAIRS = _csrc('nw_pairs.o')
+OBJ_GEODESIC = _csrc('nw_geodesic.o')
 # the translation units of libnanowrap_hip.so: (source, object, what else it is rebuilt for, flags).  The objects are linked in this order.
 UNITS = [
     # the per-iteration kernels and the C-ABI; every header of csrc/ but nw_bq.h and nw_bq_core.h is included by it (directly or through
@@ -105,6 +106,10 @@ UNITS = [
     # edges, the bin and the walk over a clamped box of cells, which the tests also compile for the CPU; it includes
     # nw_neighbours_core.h for the squared distance and the cell slack)
     (_csrc('nw_pairs.hip'), OBJ_PAIRS, [_include('nw_pairs.h'), _csrc('nw_pairs_core.h'), _csrc('nw_neighbours_core.h')] + _BQ_H, _QUERY),
+    # the distance along the mesh: edge and diagonal weights, rounds of relaxations over the half-edges, labels (nw_geodesic_core.h: the
+    # weights, the diagonal rule, one relaxation and one label step with the proof that their order is free, which the tests also compile
+    # for the CPU; it includes nw_neighbours_core.h for the squared distance)
+    (_csrc('nw_geodesic.hip'), OBJ_GEODESIC, [_include('nw_geodesic.h'), _csrc('nw_geodesic_core.h'), _csrc('nw_neighbours_core.h')] + _BQ_H, _QUERY),
 ]
 DEPS = sorted(set(d for src, _, extra, _ in UNITS for d in [src] + extra))
 
@@ -270,6 +275,14 @@ KERNEL_BUDGETS = {
     'k_pq_pairs<false>':              (56, 8 * 1024),      # up to 16 bins: 128 lanes x 16 bins x 4 bytes; the edges are scalar operands
     'k_pq_pairs<true>':               (56, 17 * 1024),     # up to 64 bins: 64 lanes x 64 bins x 4 bytes and the LDS copy of the edges (512 bytes)
     'k_pq_totals':                    (24, 2048),          # LDS = one 64-bit sum per thread
+    # the distance along the mesh (csrc/nw_geodesic.o): one lane per half-edge or per vertex, 64-bit integer atomics on D; zero scratch.  All
+    # of them reach 8 waves per SIMD
+    'k_gd_weights':                   (64, 256),           # two corners unfolded in float64 (amdgpu_waves_per_eu(8, 8)); LDS = the workgroup's count
+    'k_gd_seed':                      (16, 0),
+    'k_gd_relax':                     (32, 256),           # one arc, two distances and a candidate; LDS = the workgroup's vote
+    'k_gd_labels':                    (32, 256),
+    'k_gd_finish':                    (16, 256),           # LDS = the workgroup's two counts
+    'k_gd_totals':                    (24, 2048),          # LDS = one 64-bit sum per thread
     # what the eleven units above share (csrc/nw_bq.o), and nw_mapping.o: the exclusive scan, and the point grid of hole punching (f32) and of the metric (f64)
     'k_bq_scan_tiles':                (32, 1024),
     'k_bq_scan_bsums':                (32, 1024),
@@ -281,7 +294,7 @@ KERNEL_BUDGETS = {
     'k_bq_cell_count_f64':            (48, 0),
     'k_bq_scatter_f64':               (16, 0),
 }
-BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_DISTANCE, OBJ_NEIGHBOURS, OBJ_INTERSECTIONS, OBJ_RAYS, OBJ_VOLUME, OBJ_PROXIMITY, OBJ_MAPPING, OBJ_CLUSTERING, OBJ_PAIRS, OBJ_BQ]
+BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_DISTANCE, OBJ_NEIGHBOURS, OBJ_INTERSECTIONS, OBJ_RAYS, OBJ_VOLUME, OBJ_PROXIMITY, OBJ_MAPPING, OBJ_CLUSTERING, OBJ_PAIRS, OBJ_GEODESIC, OBJ_BQ]
 
 
 def kernel_resources(obj=None):

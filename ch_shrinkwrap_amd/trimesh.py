@@ -512,6 +512,13 @@ class TriMesh(object):
         from .mapping import surface_density
         return surface_density(points, self, band=band, **kw)
 
+    def geodesic_distance(self, sources, **kw):
+        """The distance of every vertex from the source vertices along this mesh: geodesic.geodesic_distance(self, sources, **kw)
+        -> dict(distance, source, info).  A graph distance over the edges and, across interior edges, the unfolded face diagonals: an upper
+        bound of the polyhedral geodesic, not the geodesic itself (on the device; raises without a GPU)."""
+        from .geodesic import geodesic_distance
+        return geodesic_distance(self, sources, **kw)
+
     # -- what upstream's MeshProperties module reads (evaluation.mesh_properties has the definitions).  None of them is a stored field:
     # each is computed from the face array when it is asked for and kept until the face array is replaced (a TriMesh's topology is
     # fixed: a remesher makes a new TriMesh).  euler and manifold are host work (twins and two connected-components passes, O(faces));
