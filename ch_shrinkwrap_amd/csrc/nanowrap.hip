@@ -112,6 +112,7 @@ struct nw_ctx {
     uint32_t comm_mode = 0;                // NW_FLAG_COMM_* of the current search
     DevBuf<unsigned char> comm_scratch;    // staging of host buffers given to nw_comm_all_reduce
     int64_t n_staged_copy_outs = 0, n_write_backs = 0;      // nw_debug, what = 2
+    int64_t n_blocks_captured = 0, n_blocks_replayed = 0, n_blocks_direct = 0;      // nw_debug, what = 7: which path the blocks took
     std::vector<uint64_t> comm_patterns;   // communication patterns (mode, sizes, peers) that have run one block outside a capture (nw_search)
     int comm_capture_failures = 0;         // blocks with collectives whose recording failed (RCCL calls that a stream capture does not take): after two, such blocks are launched directly
     bool direct_out = false;         // nw_search: the last update of the block writes its result into the pinned staging buffer itself
@@ -1982,7 +1983,9 @@ NW_EXPORT int nw_search_end(nw_ctx *ctx, float *pos_out, nw_iter_log *log, int *
     return NW_OK;
 }
 
-// everything a captured block bakes into its launches
+// everything a captured block bakes into its launches.  (Not in it, because no launch of the recorded range takes them: proj_key / proj_idx /
+// proj_foot -- k_projection_keys runs in nw_search_end, the re-sort in nw_search_begin --, and done_count -- k_block_done and k_copy_slice
+// are queued behind the replay by nw_search.)  tests/test_hip_block_transitions.py changes one thing at a time between blocks of a live ctx.
 static uint64_t block_graph_key(const nw_ctx *ctx)
 {
     uint64_t h = 1469598103934665603ull;
@@ -2002,7 +2005,9 @@ static uint64_t block_graph_key(const nw_ctx *ctx)
                           ctx->part_p.p, ctx->part_s.p, ctx->wv.p, ctx->state.p, ctx->logs.p, ctx->nn_stats.p, ctx->ring4.p, ctx->ring_a.p, ctx->item_done.p, ctx->query_serial.p,
                           ctx->hb_local.p, ctx->hb_slot.p, ctx->hb_slot2local.p, ctx->halo_acc.p, ctx->halo_rows.p, ctx->face_sorted ? ctx->face_orig.p : nullptr,
                           ctx->have_peers ? ctx->px_ghost.p : nullptr, ctx->have_peers ? ctx->px_owned.p : nullptr, ctx->have_peers ? ctx->px_send.p : nullptr,
-                          ctx->have_peers ? ctx->px_recv.p : nullptr};
+                          ctx->have_peers ? ctx->px_recv.p : nullptr,
+                          ctx->perm.p,                                               // attract_args(): k_nn_wave's attraction workgroups / k_attract
+                          ctx->items_by_cost ? nullptr : ctx->item_cost.p};          // k_nn_wave writes every item's duration there until the list has been ordered
     if (ctx->have_peers) { mix((uint64_t)ctx->px_ng); mix((uint64_t)ctx->px_no); for (size_t p = 0; p < ctx->px_rank.size(); ++p) { mix((uint64_t)ctx->px_rank[p]); mix((uint64_t)ctx->px_goff[p + 1]); mix((uint64_t)ctx->px_ooff[p + 1]); } }
     mix((uint64_t)ctx->hb_n); mix((uint64_t)ctx->hb_nslot); mix((uint64_t)(uintptr_t)ctx->stream);
     mix((uint64_t)(uintptr_t)ctx->comm); mix((uint64_t)ctx->comm_mode); mixp((ctx->have_boundary && ctx->have_halo_d0) ? ctx->halo_d0.p : nullptr);
@@ -2070,6 +2075,7 @@ static nw_ctx::BlockGraph *block_graph(nw_ctx *ctx, int num_iters, bool head)
     ctx->graph_next = (ctx->graph_next + 1) % 8;
     if (dst.exec) (void)hipGraphExecDestroy(dst.exec);
     dst.exec = ea; dst.key = key;
+    ctx->n_blocks_captured += 1;
     return &dst;
 }
 
@@ -2302,6 +2308,8 @@ NW_EXPORT int nw_search(nw_ctx *ctx, const float *lams, int n_lams, int num_iter
             replayed = true;
         } else (void)hipGetLastError();
     }
+    if (replayed) ctx->n_blocks_replayed += 1;      // (level 4: the head came from a graph, the last iteration follows from the host)
+    else ctx->n_blocks_direct += 1;
     for (int i = ctx->search_done; i < num_iters; ++i) {
         const int r = run_iteration(ctx);
         if (r != NW_OK) { ctx->in_search = false; return r; }
@@ -2728,7 +2736,8 @@ static int debug_nn_stats(nw_ctx *ctx, int64_t *out)
 
 // developer aids behind one entry point (not part of the drop-in surface): what = 0: counters of the NN query since the last call
 // (a = int64[NWS_COUNT + 1]; the first call switches the counting on); what = 1: the query's work list (a = int32 {p0, n}[cap], b =
-// uint32 cost[cap] (2 cap with NW_ITEM_TIMES), *n = items in the list)
+// uint32 cost[cap] (2 cap with NW_ITEM_TIMES), *n = items in the list); what = 7: which path the blocks of nw_search took so far
+// (a = int64[3]: {blocks recorded as a hipGraph, blocks replayed from one, blocks launched directly})
 NW_EXPORT int nw_debug(nw_ctx *ctx, int what, void *a, void *b, int cap, int *n)
 {
     if (what == 0) return debug_nn_stats(ctx, (int64_t *)a);
@@ -2754,6 +2763,11 @@ NW_EXPORT int nw_debug(nw_ctx *ctx, int what, void *a, void *b, int cap, int *n)
             memcpy(&kd[4], &w, 4);
         }
         if (ctx->perm.p && cap > 0) NW_HIP(hipMemcpy(a, ctx->perm.p, (size_t)std::min<int64_t>(cap, ctx->N) * sizeof(int), hipMemcpyDeviceToHost));
+        return NW_OK;
+    }
+    if (what == 7 && ctx && a) {
+        int64_t *o = (int64_t *)a;
+        o[0] = ctx->n_blocks_captured; o[1] = ctx->n_blocks_replayed; o[2] = ctx->n_blocks_direct;
         return NW_OK;
     }
     if ((what == 5 || what == 6) && ctx && a && b && n) {

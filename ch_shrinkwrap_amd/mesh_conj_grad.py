@@ -509,6 +509,13 @@ class ShrinkwrapMeshConjGrad(object):
         """do the library's pending one-off set-up now (the projection re-sort after the first block) instead of at the next search()"""
         self._native.check(self._L.nw_optimize_layout(self._h))
 
+    def graph_stats(self):
+        """which path the blocks of this native context took so far (nw_debug(what = 7)): recorded as a hipGraph, replayed from one
+        (level 4: the head of the block), launched directly from the host"""
+        out = (ctypes.c_int64 * 3)()
+        self._native.check(self._L.nw_debug(self._h, 7, out, None, 0, None))
+        return dict(captured=int(out[0]), replayed=int(out[1]), direct=int(out[2]))
+
     def nn_stats(self):
         """developer counters of the nearest-face query since the previous call (first call: switches them on)"""
         out = (ctypes.c_int64 * 17)()

@@ -356,7 +356,10 @@ int nw_accumulator_quantum(nw_ctx *ctx, double *q);
  * what = 5, 6: with NW_KD_KEEP set in the environment when the second sort runs, what its k-d partition was given, in the order of the
  *   sorted foot-point keys (the tests restate the partition from it: csrc/nw_partition_core.h).  5: a = uint32 key[cap], b = float
  *   {foot x, y, z, signed height}[cap]; 6: a = int32 nearest face (the library's own id)[cap], b = int32 the caller's index[cap];
- *   *n = localizations kept (0: nothing). */
+ *   *n = localizations kept (0: nothing).
+ * what = 7: a = int64 out[3]: which path the blocks of nw_search took so far -- {blocks recorded as a hipGraph (nw_optimize_layout's
+ *   pre-recording included), blocks replayed from a recorded graph (at profiling level 4: the head of the block), blocks whose launches
+ *   all came from the host}.  A recording that fails silently shows as direct blocks, a key that changes as one more recording. */
 int nw_debug(nw_ctx *ctx, int what, void *a, void *b, int cap, int *n);
 
 /* ---- the block-boundary remesher on the device (ABI 6) ---------------------------------------------------------------------------
