@@ -46,6 +46,7 @@ OBJ_MAPPING = _csrc('nw_mapping.o')
 OBJ_CLUSTERING = _csrc('nw_clustering.o')
 OBJ_PAIRS = _csrc('nw_pairs.o')
 OBJ_GEODESIC = _csrc('nw_geodesic.o')
+OBJ_SKELETON = _csrc('nw_skeleton.o')
 # the translation units of libnanowrap_hip.so: (source, object, what else it is rebuilt for, flags).  The objects are linked in this order.
 UNITS = [
     # the per-iteration kernels and the C-ABI; every header of csrc/ but nw_bq.h and nw_bq_core.h is included by it (directly or through
@@ -110,6 +111,10 @@ UNITS = [
     # weights, the diagonal rule, one relaxation and one label step with the proof that their order is free, which the tests also compile
     # for the CPU; it includes nw_neighbours_core.h for the squared distance)
     (_csrc('nw_geodesic.hip'), OBJ_GEODESIC, [_include('nw_geodesic.h'), _csrc('nw_geodesic_core.h'), _csrc('nw_neighbours_core.h')] + _BQ_H, _QUERY),
+    # the level-set skeleton of a mesh: bands of a field, their pieces joined by a union-find over the half-edges, node sums in integers,
+    # arcs (nw_skeleton_core.h: the band rule, the piece index, the crossing point, the quantisation and the proof that no sum overflows,
+    # which the tests also compile for the CPU; it includes nothing of the project's)
+    (_csrc('nw_skeleton.hip'), OBJ_SKELETON, [_include('nw_skeleton.h'), _csrc('nw_skeleton_core.h')] + _BQ_H, _QUERY),
 ]
 DEPS = sorted(set(d for src, _, extra, _ in UNITS for d in [src] + extra))
 
@@ -283,6 +288,18 @@ KERNEL_BUDGETS = {
     'k_gd_labels':                    (32, 256),
     'k_gd_finish':                    (16, 256),           # LDS = the workgroup's two counts
     'k_gd_totals':                    (24, 2048),          # LDS = one 64-bit sum per thread
+    # the level-set skeleton (csrc/nw_skeleton.o): one lane per vertex, face, half-edge or piece; a union-find with compare-and-swaps and
+    # 64-bit integer atomic adds whose results are not read; zero scratch (a piece's corners are picked with selects).  All of them are
+    # meant to reach 8 waves per SIMD (512 // VGPRs, capped at 8), k_sk_sums with two registers to spare
+    'k_sk_bands':                     (32, 512),           # three corners' bands; LDS = the four waves' span sums and largest bands, two votes
+    'k_sk_totals':                    (24, 2048),          # LDS = one 64-bit word per thread
+    'k_sk_init':                      (16, 0),             # the binary search in piece_start
+    'k_sk_hook':                      (32, 0),             # the edge's band range and the two roots of a union
+    'k_sk_compress':                  (16, 0),
+    'k_sk_number':                    (16, 0),
+    'k_sk_sums':                      (64, 0),             # three corners in float64, two crossing points, twelve 64-bit terms
+    'k_sk_arcs':                      (16, 0),
+    'k_sk_vertex':                    (16, 0),
     # what the eleven units above share (csrc/nw_bq.o), and nw_mapping.o: the exclusive scan, and the point grid of hole punching (f32) and of the metric (f64)
     'k_bq_scan_tiles':                (32, 1024),
     'k_bq_scan_bsums':                (32, 1024),
@@ -294,7 +311,7 @@ KERNEL_BUDGETS = {
     'k_bq_cell_count_f64':            (48, 0),
     'k_bq_scatter_f64':               (16, 0),
 }
-BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_DISTANCE, OBJ_NEIGHBOURS, OBJ_INTERSECTIONS, OBJ_RAYS, OBJ_VOLUME, OBJ_PROXIMITY, OBJ_MAPPING, OBJ_CLUSTERING, OBJ_PAIRS, OBJ_GEODESIC, OBJ_BQ]
+BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_DISTANCE, OBJ_NEIGHBOURS, OBJ_INTERSECTIONS, OBJ_RAYS, OBJ_VOLUME, OBJ_PROXIMITY, OBJ_MAPPING, OBJ_CLUSTERING, OBJ_PAIRS, OBJ_GEODESIC, OBJ_SKELETON, OBJ_BQ]
 
 
 def kernel_resources(obj=None):

@@ -519,6 +519,13 @@ class TriMesh(object):
         from .geodesic import geodesic_distance
         return geodesic_distance(self, sources, **kw)
 
+    def skeleton(self, **kw):
+        """The centreline graph of this mesh: skeleton.level_set_skeleton(self, **kw) -> dict(nodes, arcs, vertex_node, ...).  A level-set
+        diagram of one field (by default the geodesic graph distance of a double sweep), not a medial axis: it depends on the source, and
+        loops narrower than a band vanish (on the device; raises without a GPU)."""
+        from .skeleton import level_set_skeleton
+        return level_set_skeleton(self, **kw)
+
     # -- what upstream's MeshProperties module reads (evaluation.mesh_properties has the definitions).  None of them is a stored field:
     # each is computed from the face array when it is asked for and kept until the face array is replaced (a TriMesh's topology is
     # fixed: a remesher makes a new TriMesh).  euler and manifold are host work (twins and two connected-components passes, O(faces));
