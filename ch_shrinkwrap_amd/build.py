@@ -90,8 +90,8 @@ UNITS = [
     # nw_intersections_core.h)
     (_csrc('nw_proximity.hip'), OBJ_PROXIMITY, [_include('nw_proximity.h'), _csrc('nw_proximity_core.h'), _csrc('nw_distance_core.h'),
                                                 _csrc('nw_intersections_core.h')] + _BQ_H, _QUERY),
-    # what the eleven above share (csrc/nw_bq.h), and the two below them: the exclusive scan and the point grid's bounding box and
-    # counting sort, float and double
+    # what the eleven above share (csrc/nw_bq.h), and the two below them: the exclusive scan, the point grid's bounding box and
+    # counting sort, float and double, and the mesh query units' face grid (its arithmetic is in nw_bq_core.h)
     (_csrc('nw_bq.hip'), OBJ_BQ, _BQ, _QUERY),
     # localizations mapped onto the mesh: per-vertex mass, per-face counts and value sums as integers (nw_mapping_core.h: the weights, the
     # quantisation, the limbs and the vertex areas, which the tests also compile for the CPU; it includes nw_volume_core.h for the capped
@@ -221,8 +221,6 @@ KERNEL_BUDGETS = {
     'k_sim_copy_keep':                (16, 0),
     'k_sim_copy_emit':                (88, 0),             # three normals and three photon draws per copy, unrolled: 5 waves per SIMD
     # the point-to-mesh distance (csrc/nw_distance.o): an end-of-fit query in float64, budgeted for zero scratch and against silent growth
-    'k_md_face_setup':                (64, 0),
-    'k_md_rho_reduce':                (24, 64),            # LDS = the four waves' maxima and sums
     'k_md_query':                     (128, 64),           # float64 query, best record (d2, d, closest point, face, feature) and one exact test in flight: 4 waves per SIMD; LDS = the four waves' sums
     'k_md_sum_final':                 (16, 64),
     # the k-th-neighbour distance (csrc/nw_neighbours.o): set-up queries in float64, budgeted for zero scratch (a lane's k best live in LDS,
@@ -231,21 +229,15 @@ KERNEL_BUDGETS = {
     'k_kn_nodes':                     (64, 32 * 1024),
     # the self-intersection check (csrc/nw_intersections.o): an end-of-fit query in float64, budgeted for zero scratch (the corners of a
     # shared-vertex pair are picked with selects, never from an array indexed at run time) and against silent growth
-    'k_mx_face_setup':                (64, 0),
-    'k_mx_rho_reduce':                (24, 64),            # LDS = the four waves' maxima and sums
     'k_mx_count':                     (168, 0),            # the lane's own face in float64 (ids, corners, centroid, radius), the candidate's, and the predicate's two normals and triple products: 3 waves per SIMD
     'k_mx_emit':                      (168, 0),
     'k_mx_stats':                     (64, 0),             # the walk without the predicate
     'k_mx_totals':                    (24, 128),           # LDS = the four waves' three sums
     # ray casting (csrc/nw_rays.o): an end-of-fit query in float64, budgeted for zero scratch and against silent growth
-    'k_rc_face_setup':                (64, 0),
-    'k_rc_rho_reduce':                (24, 64),            # LDS = the four waves' maxima and sums
     'k_rc_first':                     (128, 0),            # the ray, the piece, the candidate's centroid and one exact test in flight: 4 waves per SIMD (some of the walk's uniform values sit in VGPR lanes: no scratch)
     'k_rc_count':                     (128, 0),            # the same walk without the early exit, and the count: 4 waves per SIMD
     'k_rc_totals':                    (24, 96),            # LDS = the four waves' three sums
     # the signed-distance volume (csrc/nw_volume.o): the query's walk with a band, one lane per lattice node; no atomics, zero scratch
-    'k_vx_face_setup':                (64, 0),
-    'k_vx_rho_reduce':                (24, 64),            # LDS = the four waves' maxima and sums
     'k_vx_nodes':                     (128, 192),          # k_md_query's record and walk, the band and six counters: 4 waves per SIMD; LDS = the four waves' six counters
     'k_vx_seed':                      (128, 64),           # one exact test in flight; LDS = the four waves' (d2, face)
     'k_vx_sweep':                     (24, 0),
@@ -254,15 +246,12 @@ KERNEL_BUDGETS = {
     # the mesh-to-mesh distance (csrc/nw_proximity.o): the query's walk with a band, one lane per face of the querying mesh; no atomics of its
     # own, zero scratch (the corners of a candidate and of the 3 x 3 edge pairs are picked with selects inside loops that stay loops, never from an array
     # indexed at run time)
-    'k_mm_face_setup':                (56, 0),
-    'k_mm_rho_reduce':                (24, 64),            # LDS = the four waves' maxima and sums
     'k_mm_query':                     (168, 160),          # the lane's face (centroid, radius, corner pointers), the walk's cell ranges and (d2, face), both triangles in float64 with their normals and one point-triangle or edge-edge candidate in flight: 3 waves per SIMD (amdgpu_waves_per_eu(3, 8)); LDS = the four waves' five counters
     'k_mm_finish':                    (136, 0),            # one pair test with its kind and two closest points: 3 waves per SIMD
     'k_mm_totals':                    (32, 160),           # LDS = the four waves' five counters
     # localizations on the mesh (csrc/nw_mapping.o): the volume unit's walk with one lane per localization, then integer atomics whose
     # results are not read; zero scratch (the weights are written with constant indices, the corners' atomics are spelled out)
     'k_lm_face_setup':                (64, 0),
-    'k_lm_rho_reduce':                (24, 64),            # LDS = the four waves' maxima and sums
     'k_lm_map':                       (128, 96),           # k_vx_nodes' record and walk, the weights and one product's limbs: 4 waves per SIMD; LDS = the four waves' three counters
     'k_lm_totals':                    (32, 96),            # LDS = the four waves' three counters
     # DBSCAN clustering (csrc/nw_clustering.o): one lane per point in cell order, the walk's visitor in registers; zero scratch.  All of them
@@ -310,6 +299,9 @@ KERNEL_BUDGETS = {
     'k_bq_bbox_f64':                  (48, 0),             # six 64-bit keys per thread
     'k_bq_cell_count_f64':            (48, 0),
     'k_bq_scatter_f64':               (16, 0),
+    # and the face grid of the six mesh query units (distance, intersections, rays, volume, proximity, mapping): a face's float64 centroid and radius
+    'k_bq_face_setup':                (56, 0),
+    'k_bq_rho_reduce':                (24, 64),            # LDS = the four waves' maxima and sums
 }
 BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_DISTANCE, OBJ_NEIGHBOURS, OBJ_INTERSECTIONS, OBJ_RAYS, OBJ_VOLUME, OBJ_PROXIMITY, OBJ_MAPPING, OBJ_CLUSTERING, OBJ_PAIRS, OBJ_GEODESIC, OBJ_SKELETON, OBJ_BQ]
 

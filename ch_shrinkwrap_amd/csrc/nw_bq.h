@@ -1,9 +1,11 @@
 // What the query units (nw_holepunch.hip, nw_surgery.hip, nw_isosurface.hip, nw_evaluation.hip, nw_simulation.hip) share: the device
 // buffer and the staging of host arrays into it, the base of their contexts with its create / destroy / last_error bodies, the HIP-call
 // macro, the host checks of a mesh and of finiteness, the ordered-key maps, the exclusive scan, the point grid (bounding box, sizing,
-// counting sort by cell, the cell index of a coordinate) in float and in double, and the host loop of the 64-bit radix select.  Kernels
-// and host entries are in nw_bq.hip; what needs no HIP is in nw_bq_core.h.  Each C-ABI keeps its own status codes and error texts:
-// everything here that can fail returns a hipError_t or a flag, and its user says what that means.
+// counting sort by cell, the cell index of a coordinate) in float and in double, the face grid of the six mesh query units (the
+// intake of a mesh: centroids, radii, their reduction, the centroids' box; and their binning at a cell size), and the host loop of the
+// 64-bit radix select.  Kernels and host entries are in nw_bq.hip; what needs no HIP is in nw_bq_core.h.  Each C-ABI keeps its own
+// status codes and error texts: everything here that can fail returns a hipError_t, a flag or a FaceStatus, and its user says what that
+// means (face_fail holds the words the six mesh units share; the prefix and the status are the unit's).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -182,6 +184,108 @@ template <class T> hipError_t bounds(hipStream_t stream, DevBuf &keys, const T *
 // `cursor` are work buffers; the stream is synchronised.
 template <class T> hipError_t build_grid(hipStream_t stream, const T *xyz, int n, const Grid<T> &g, DevBuf &cell, DevBuf &cursor, DevBuf &scan_tmp,
                                          DevBuf &cstart, DevBuf &sorted, int *total);
+
+// ---- face grid (nw_bq.hip) --------------------------------------------------------------------------------------------------------------
+// What the mesh query units (nw_distance, nw_intersections, nw_rays, nw_volume, nw_proximity, nw_mapping) do with a mesh before they walk
+// it: every face's float64 centroid and radius rho_f (face_centroid, enlarged by BQ_FACE_RHO_SLACK), rho_max and the mean rho_f, the
+// centroids' box, and the centroids binned into the double point grid, a sorted point carrying its face id.
+
+// how taking a mesh in or binning it ended; every C-ABI gives that its own status and its own text (face_fail)
+enum FaceCheck {
+    FACES_OK = 0,
+    FACES_BAD_SIZE,           // a NULL array or a size out of range
+    FACES_BAD_POSITION,       // a vertex position is not finite
+    FACES_BAD_INDEX,          // a face index outside the vertices
+    FACES_NONFINITE,          // a face's centroid or radius is not a finite double
+    FACES_BAD_EXTENT,         // the mesh's extent is not a finite double
+    FACES_NO_GRID,            // no cell size keeps the grid within its cap
+    FACES_BAD_TOTAL,          // the cell counts do not add up to the faces
+    FACES_HIP                 // a HIP call failed: `hip`, and `call` names it
+};
+
+struct FaceStatus {
+    FaceCheck check = FACES_OK;
+    hipError_t hip = hipSuccess;
+    const char *call = "";
+    FaceStatus(FaceCheck c = FACES_OK) : check(c) {}
+    bool ok() const { return check == FACES_OK; }
+};
+
+// the host checks of a mesh's arguments, in this order and before any HIP call: NULL or sizes beyond the int kernels, finiteness of pos,
+// range of the face indices
+inline FaceStatus check_faces(const float *pos, int64_t nv, const int32_t *faces, int64_t nf)
+{
+    if (!pos || !faces || nv < 3 || nf < 1 || nv > (1ll << 30) || nf > (1ll << 29)) return FACES_BAD_SIZE;
+    if (!all_finite(pos, 3 * nv)) return FACES_BAD_POSITION;
+    for (int64_t i = 0; i < 3 * nf; ++i)
+        if (faces[i] < 0 || faces[i] >= nv) return FACES_BAD_INDEX;
+    return FACES_OK;
+}
+
+// a half-edge twin table: -1 (a border) or an involution within [0, 3F)
+inline bool twin_ok(const int32_t *twin, int64_t nf)
+{
+    const int64_t nh = 3 * nf;
+    for (int64_t h = 0; h < nh; ++h) {
+        const int32_t t = twin[h];
+        if (t == -1) continue;
+        if (t < 0 || t >= nh || twin[t] != h) return false;
+    }
+    return true;
+}
+
+// the statuses of a C-ABI that a FaceStatus maps to
+struct FaceCodes { int badarg, nonfinite, nomem, hip; };
+
+// a failed FaceStatus as the ABI's status, with "<who>: <what>" in last_error (who = the ABI's function)
+inline int face_fail(Ctx *ctx, const char *who, const FaceStatus &s, const FaceCodes &c)
+{
+    const std::string w = std::string(who) + ": ";
+    switch (s.check) {
+    case FACES_BAD_SIZE: return fail(ctx, c.badarg, w + "a NULL array or a size out of range");
+    case FACES_BAD_POSITION: return fail(ctx, c.nonfinite, w + "a vertex position is not finite");
+    case FACES_BAD_INDEX: return fail(ctx, c.badarg, w + "a face index outside the vertices");
+    case FACES_NONFINITE: return fail(ctx, c.nonfinite, w + "a face's centroid or radius is not a finite double");
+    case FACES_BAD_EXTENT: return fail(ctx, c.badarg, w + "the mesh's extent is not a finite double");
+    case FACES_NO_GRID: return fail(ctx, c.badarg, w + "no cell size keeps the grid within its cap");
+    case FACES_BAD_TOTAL: return fail(ctx, c.hip, w + "the cell counts do not add up to the faces");
+    default: return fail(ctx, s.hip == hipErrorOutOfMemory ? c.nomem : c.hip, w + s.call + ": " + hipGetErrorString(s.hip));
+    }
+}
+
+// centroid and radius of faces[0..nf) into cen (3 per face) and rho on `stream` (k_bq_face_setup); nothing is waited for
+hipError_t face_setup(hipStream_t stream, const float *pos, const int *faces, int nf, double *cen, double *rho);
+
+struct FaceGrid {
+    int nf = 0;                   // 0: no mesh
+    int64_t nv = 0;
+    double rho_max = 0.0, rho_mean = 0.0;
+    Grid<double> g{};             // lo, hi: the centroids' box; h, dims: the grid at hand
+    double h_start = 0.0;         // the cell size the grid at hand was sized from (0: none)
+    DevBuf mpos, mfaces, cen, rho, red, mm, cell, ccount, cstart, sorted, scan_tmp;
+
+    // a unit's own kernel in place of k_bq_face_setup, queued on the stream between the uploads and the reduction (the mapping
+    // unit's also scatters the faces' areas)
+    typedef hipError_t (*Setup)(void *user, hipStream_t stream, const float *pos, int64_t nv, const int *faces, int nf, double *cen, double *rho);
+
+    // Takes in a mesh that check_faces has passed: the uploads, centroids and radii, their reduction (k_bq_rho_reduce), the centroids'
+    // box, and the checks that all of it is finite.  The stream is synchronised: the caller's arrays are free afterwards.  nf stays 0
+    // unless all is well, and the grid at hand is forgotten either way.
+    FaceStatus set_faces(hipStream_t stream, const float *pos, int64_t n_vertices, const int32_t *faces, int64_t n_faces, Setup own = nullptr,
+                         void *user = nullptr);
+
+    // the widest axis of the centroids' box
+    double emax() const
+    {
+        double e = 0.0;
+        for (int d = 0; d < 3; ++d) e = std::max(e, g.hi[d] - g.lo[d]);
+        return e;
+    }
+
+    // The grid for the starting cell size h0 (face_cell of the unit's candidate): the one at hand if it was sized from the same h0, else
+    // the centroids binned anew (face_bins, build_grid), which synchronises the stream.
+    FaceStatus bin(hipStream_t stream, double h0);
+};
 
 // ---- radix select -----------------------------------------------------------------------------------------------------------------------
 // The key of a given rank among the 64-bit keys that `pass` sees, a byte per pass from `shift` down.  pass(prefix, shift, hist) launches

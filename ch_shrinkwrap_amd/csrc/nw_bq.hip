@@ -3,6 +3,7 @@
 //   k_bq_scan_*                        the exclusive scan: int, three launches, exact (the per-iteration scan of nanowrap.hip is another one)
 //   k_bq_bbox_*                        bounding box (ordered keys, atomicMin / atomicMax) and finiteness of a cloud
 //   k_bq_cell_count_*, k_bq_scatter_*  counting sort of a cloud by cell of its grid, with the scan between them
+//   k_bq_face_setup, k_bq_rho_reduce   the face grid of the mesh query units: a face's float64 centroid and radius, rho_max and the sum
 // The grid's kernels are written once as templates over the coordinate type and wrapped in plain kernels _f32 / _f64:
 // build.kernel_resources names a kernel without its template arguments, so two instantiations of one template would share a budget row.
 //
@@ -213,3 +214,92 @@ template hipError_t bq::bounds<float>(hipStream_t, DevBuf &, const float *, int,
 template hipError_t bq::bounds<double>(hipStream_t, DevBuf &, const double *, int, const double *, int, Grid<double> *, bool[2]);
 template hipError_t bq::build_grid<float>(hipStream_t, const float *, int, const Grid<float> &, DevBuf &, DevBuf &, DevBuf &, DevBuf &, DevBuf &, int *);
 template hipError_t bq::build_grid<double>(hipStream_t, const double *, int, const Grid<double> &, DevBuf &, DevBuf &, DevBuf &, DevBuf &, DevBuf &, int *);
+
+// ---- face grid --------------------------------------------------------------------------------------------------------------------------
+// one thread per face: the float64 centroid and rho_f, a hair enlarged so that rounding can only make a bound weaker
+__global__ __launch_bounds__(BQ_BLOCK) void k_bq_face_setup(const float *__restrict__ pos, const int *__restrict__ faces, int nf,
+                                                            double *__restrict__ cen, double *__restrict__ rho)
+{
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= nf) return;
+    const int a = faces[3 * (int64_t)f], b = faces[3 * (int64_t)f + 1], c = faces[3 * (int64_t)f + 2];
+    double m[3];
+    const double r = bq::face_centroid(pos + 3 * (int64_t)a, pos + 3 * (int64_t)b, pos + 3 * (int64_t)c, m);
+    cen[3 * (int64_t)f] = m[0];
+    cen[3 * (int64_t)f + 1] = m[1];
+    cen[3 * (int64_t)f + 2] = m[2];
+    rho[f] = r * (1.0 + BQ_FACE_RHO_SLACK);
+}
+
+// out[0] = the largest rho, out[1] = their sum: one workgroup, a butterfly within each wave, then the four waves in order.  The sum is
+// an input to the cell size and so to every walk's statistics: its order is fixed.
+__global__ __launch_bounds__(BQ_BLOCK) void k_bq_rho_reduce(const double *__restrict__ rho, int nf, double *__restrict__ out)
+{
+    __shared__ double s_m[BQ_BLOCK / 64], s_s[BQ_BLOCK / 64];
+    double m = 0.0, s = 0.0;
+    for (int j = threadIdx.x; j < nf; j += BQ_BLOCK) { m = fmax(m, rho[j]); s += rho[j]; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { m = fmax(m, __shfl_xor(m, o, 64)); s += __shfl_xor(s, o, 64); }
+    if ((threadIdx.x & 63) == 0) { s_m[threadIdx.x >> 6] = m; s_s[threadIdx.x >> 6] = s; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        out[0] = fmax(fmax(s_m[0], s_m[1]), fmax(s_m[2], s_m[3]));
+        out[1] = ((s_s[0] + s_s[1]) + s_s[2]) + s_s[3];
+    }
+}
+
+hipError_t bq::face_setup(hipStream_t stream, const float *pos, const int *faces, int nf, double *cen, double *rho)
+{
+    hipLaunchKernelGGL(k_bq_face_setup, dim3(nblk(nf)), dim3(BQ_BLOCK), 0, stream, pos, faces, nf, cen, rho);
+    return hipGetLastError();
+}
+
+// (returns the FaceStatus of a failed HIP call with the call's text)
+#define BQ_FACE_TRY(expr)                                                                                      \
+    do {                                                                                                       \
+        const hipError_t e_ = (expr);                                                                          \
+        if (e_ != hipSuccess) { FaceStatus s_(FACES_HIP); s_.hip = e_; s_.call = #expr; return s_; }           \
+    } while (0)
+
+bq::FaceStatus bq::FaceGrid::set_faces(hipStream_t stream, const float *pos, int64_t n_vertices, const int32_t *faces, int64_t n_faces, Setup own,
+                                       void *user)
+{
+    nf = 0;
+    nv = 0;
+    h_start = 0.0;
+    const int n = (int)n_faces;
+    BQ_FACE_TRY(upload(stream, mpos, pos, 3 * n_vertices));
+    BQ_FACE_TRY(upload(stream, mfaces, faces, 3 * n_faces));
+    BQ_FACE_TRY(cen.ensure(sizeof(double) * 3 * (size_t)n));
+    BQ_FACE_TRY(rho.ensure(sizeof(double) * (size_t)n));
+    BQ_FACE_TRY(red.ensure(sizeof(double) * 2));
+    if (own) BQ_FACE_TRY(own(user, stream, mpos.as<float>(), n_vertices, mfaces.as<int>(), n, cen.as<double>(), rho.as<double>()));
+    else BQ_FACE_TRY(face_setup(stream, mpos.as<float>(), mfaces.as<int>(), n, cen.as<double>(), rho.as<double>()));
+    hipLaunchKernelGGL(k_bq_rho_reduce, dim3(1), dim3(BQ_BLOCK), 0, stream, rho.as<double>(), n, red.as<double>());
+    BQ_FACE_TRY(hipGetLastError());
+    double r[2] = {0.0, 0.0};
+    BQ_FACE_TRY(hipMemcpyAsync(r, red.p, sizeof(r), hipMemcpyDeviceToHost, stream));
+    BQ_FACE_TRY(hipStreamSynchronize(stream));                    // (r is a stack array, and the uploads' sources are the caller's)
+    bool finite[2];
+    BQ_FACE_TRY(bounds<double>(stream, mm, cen.as<double>(), n, nullptr, 0, &g, finite));
+    if (!finite[0] || !std::isfinite(r[0]) || !std::isfinite(r[1])) return FACES_NONFINITE;
+    if (!std::isfinite(emax())) return FACES_BAD_EXTENT;
+    rho_max = r[0];
+    rho_mean = r[1] / (double)n;
+    nv = n_vertices;
+    nf = n;
+    return FACES_OK;
+}
+
+bq::FaceStatus bq::FaceGrid::bin(hipStream_t stream, double h0)
+{
+    const double ext[3] = {g.hi[0] - g.lo[0], g.hi[1] - g.lo[1], g.hi[2] - g.lo[2]};
+    const FaceBins b = face_bins(nf, ext, h0, &h_start, &g.h, g.dims);
+    if (b == FACE_BINS_KEPT) return FACES_OK;
+    if (b == FACE_BINS_NONE) return FACES_NO_GRID;
+    int total = -1;
+    BQ_FACE_TRY(build_grid<double>(stream, cen.as<double>(), nf, g, cell, ccount, scan_tmp, cstart, sorted, &total));
+    if (total != nf) return FACES_BAD_TOTAL;
+    h_start = h0;
+    return FACES_OK;
+}

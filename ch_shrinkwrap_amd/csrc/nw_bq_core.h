@@ -1,5 +1,7 @@
-// The part of nw_bq.h that needs no HIP: the sizing of a point grid and the walk of a radix select.  The query units get it through
-// nw_bq.h; tests/test_bq_core_cpu.py compiles it for the CPU with g++.  Without a HIP compiler BQ_HD is plain `inline`.
+// The part of nw_bq.h that needs no HIP: the sizing of a point grid, the mesh query units' face grid (a face's centroid and radius, the
+// cell size, when to bin anew) and the walk of a radix select.  The query units get it through nw_bq.h, and nw_distance_core.h and
+// nw_intersections_core.h include it for the centroid; tests/test_bq_core_cpu.py compiles it for the CPU with g++.  Without a HIP
+// compiler BQ_HD is plain `inline`.
 #pragma once
 #include <cstdint>
 #include <cmath>
@@ -37,6 +39,58 @@ inline bool size_grid(const GridRule &rule, int64_t n, const double ext[3], doub
         *h *= 1.1;
     }
     return (int64_t)dims[0] * dims[1] * dims[2] <= cap;
+}
+
+// ---- the face grid of the mesh query units: a face's ball, the cell size, the decision to bin -------------------------------------------
+// The centroid of a face in float64, ((a + b) + c) / 3 per axis, and rho = the largest distance from it to a corner (the root of the
+// largest of (ex ex + ey ey) + ez ez over the corners, e = corner - centroid, starting from 0): every point of the face lies within rho
+// of the centroid.  The one definition: the set-up kernels store it and the walks that compute it again rely on getting the same bits,
+// so nothing may be contracted into an fma (-ffp-contract=off).  S = float (vertex positions) or double (positions already widened).
+template <class S> BQ_HD double face_centroid(const S *a, const S *b, const S *c, double cen[3])
+{
+    double rho2 = 0.0;
+    for (int d = 0; d < 3; ++d) cen[d] = (((double)a[d] + (double)b[d]) + (double)c[d]) / 3.0;
+    const S *v[3] = {a, b, c};
+    for (int k = 0; k < 3; ++k) {
+        const double ex = (double)v[k][0] - cen[0], ey = (double)v[k][1] - cen[1], ez = (double)v[k][2] - cen[2];
+        rho2 = fmax(rho2, (ex * ex + ey * ey) + ez * ez);
+    }
+    return sqrt(rho2);
+}
+
+// the stored rho_f is face_centroid's times 1 + this: far above the rounding of a float64 distance, far below what matters, so that
+// rounding can only make a bound weaker
+#define BQ_FACE_RHO_SLACK 1e-9
+
+// at most max(16 F, 65536) cells, up to 2^26; at most 1025 an axis; 400 widening steps
+const GridRule FACE_GRID_RULE = {16, 1ll << 26, 1025, 400};
+
+// The cell size a face grid starts from: the unit's candidate, at least a 1024th of the widest axis of the centroids' box (emax); 1 for a
+// mesh without extent, emax where that is not a positive finite number (an infinite band).  The candidates: 2 m for the fixed grids of
+// the distance, intersection and ray units (m = the mean rho_f: a face or two per occupied cell of a surface), band_cell for the volume
+// and mapping units, nwm_band_cell (nw_proximity_core.h) for the proximity unit.  m = sum / F, and 2 (sum / F) = (2 sum) / F because
+// doubling is exact: only this form is kept.
+inline double face_cell(double candidate, double emax)
+{
+    if (!(emax > 0.0)) return 1.0;
+    const double h = std::max(candidate, emax / 1024.0);
+    return (h > 0.0 && std::isfinite(h)) ? h : emax;
+}
+
+// the candidate of a band d_cap: 2 m or half of d_cap + rho_max, whichever is larger -- a far query then ends its walk after three or
+// four rings, a few hundred cell ranges
+inline double band_cell(double rho_mean, double rho_max, double d_cap) { return std::max(2.0 * rho_mean, (d_cap + rho_max) / 2.0); }
+
+// The sizing half of FaceGrid::bin (nw_bq.h).  *h_start = the cell size the grid at hand was sized from (0: there is none).  A grid sized
+// from the same h0 is kept; else *h_start = 0 and h, dims are sized anew from h0, and the caller sets *h_start = h0 once it has binned.
+enum FaceBins { FACE_BINS_KEPT = 0, FACE_BINS_NEW = 1, FACE_BINS_NONE = 2 };      // NONE: no cell size keeps the grid within its cap
+
+inline FaceBins face_bins(int64_t nf, const double ext[3], double h0, double *h_start, double *h, int dims[3])
+{
+    if (*h_start == h0) return FACE_BINS_KEPT;
+    *h_start = 0.0;
+    *h = h0;
+    return size_grid(FACE_GRID_RULE, nf, ext, h, dims) ? FACE_BINS_NEW : FACE_BINS_NONE;
 }
 
 // ---- radix select over 64-bit keys, a byte per pass from the top ------------------------------------------------------------------------

@@ -1,10 +1,11 @@
 // The exact distance from points to a triangle mesh on the device (MI355X, gfx950): include/nw_distance.h.
 //
-//   nwd_set_mesh    k_md_face_setup   one thread per face: the float64 centroid and rho_f, the largest centroid-to-corner distance
-//                                     (nw_distance_core.h), a hair enlarged so that rounding can only make a bound weaker
-//                   k_md_rho_reduce   rho_max and the sum of rho_f, one workgroup, a fixed order
-//                   (bq::bounds, bq::size_grid, bq::build_grid)   the query units' shared point grid in double over the centroids;
-//                                     a sorted point carries its face id
+//   nwd_set_mesh    (bq::FaceGrid::set_faces)   the mesh query units' shared intake (nw_bq.h): k_bq_face_setup, one thread per face, the
+//                                     float64 centroid and rho_f, the largest centroid-to-corner distance, a hair enlarged so that
+//                                     rounding can only make a bound weaker; k_bq_rho_reduce, rho_max and the sum of rho_f, one
+//                                     workgroup, a fixed order; bq::bounds, the centroids' box
+//                   (bq::FaceGrid::bin)   the shared point grid in double over the centroids (bq::size_grid, bq::build_grid); a sorted
+//                                     point carries its face id
 //   nwd_query       (bq::bounds)      finiteness of the queries
 //                   k_md_query        one thread per query: rings of cells around its own, as k_ev_nearest walks them, until
 //                                     sqrt(lbd^2 + out^2) - rho_max exceeds the best distance; a centroid whose |p - c_f| - rho_f
@@ -14,9 +15,9 @@
 //                                     of dist^2 in a fixed order
 //                   k_md_sum_final    the blocks' partial sums, one workgroup, a fixed order
 //
-// The scan, the point grid, the device buffer with its staging and the context's scaffolding are the query units' shared ones (nw_bq.h);
-// what is this unit's own about the grid is its starting cell size (twice the mean rho_f: a face or two per occupied cell) and its
-// limits (NWD_GRID_RULE).  All stores are vector stores; no kernel uses scratch (build.py's KERNEL_BUDGETS checks it).
+// The scan, the point grid, the face grid, the device buffer with its staging and the context's scaffolding are the query units' shared
+// ones (nw_bq.h); what is this unit's own about the grid is its starting cell size (twice the mean rho_f: a face or two per occupied
+// cell).  All stores are vector stores; no kernel uses scratch (build.py's KERNEL_BUDGETS checks it).
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cmath>
@@ -30,38 +31,7 @@
 
 #define NWD_EXPORT extern "C" __attribute__((visibility("default")))
 #define NWD_BLOCK 256
-#define NWD_SLACK 1e-9            // relative slack of every bound: far above the rounding of a float64 distance, far below what matters
-
-// ---- set-up ---------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(NWD_BLOCK) void k_md_face_setup(const float *__restrict__ pos, const int *__restrict__ faces, int nf,
-                                                             double *__restrict__ cen, double *__restrict__ rho)
-{
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= nf) return;
-    const int a = faces[3 * (int64_t)f], b = faces[3 * (int64_t)f + 1], c = faces[3 * (int64_t)f + 2];
-    double m[3];
-    const double r = nwd_face_centroid(pos + 3 * (int64_t)a, pos + 3 * (int64_t)b, pos + 3 * (int64_t)c, m);
-    cen[3 * (int64_t)f] = m[0];
-    cen[3 * (int64_t)f + 1] = m[1];
-    cen[3 * (int64_t)f + 2] = m[2];
-    rho[f] = r * (1.0 + NWD_SLACK);
-}
-
-// out[0] = the largest rho, out[1] = their sum
-__global__ __launch_bounds__(NWD_BLOCK) void k_md_rho_reduce(const double *__restrict__ rho, int nf, double *__restrict__ out)
-{
-    __shared__ double s_m[NWD_BLOCK / 64], s_s[NWD_BLOCK / 64];
-    double m = 0.0, s = 0.0;
-    for (int j = threadIdx.x; j < nf; j += NWD_BLOCK) { m = fmax(m, rho[j]); s += rho[j]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { m = fmax(m, __shfl_xor(m, o, 64)); s += __shfl_xor(s, o, 64); }
-    if ((threadIdx.x & 63) == 0) { s_m[threadIdx.x >> 6] = m; s_s[threadIdx.x >> 6] = s; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        out[0] = fmax(fmax(s_m[0], s_m[1]), fmax(s_m[2], s_m[3]));
-        out[1] = ((s_s[0] + s_s[1]) + s_s[2]) + s_s[3];
-    }
-}
+#define NWD_SLACK BQ_FACE_RHO_SLACK   // relative slack of every bound: far above the rounding of a float64 distance, far below what matters
 
 // ---- the query --------------------------------------------------------------------------------------------------------------------------
 struct md_best {
@@ -176,12 +146,9 @@ using bq::fail;
 using bq::nblk;
 
 struct nwd_ctx : bq::Ctx {
-    // the mesh of the last nwd_set_mesh and its grid
-    int nf = 0;                   // 0: the context holds no mesh
+    bq::FaceGrid m;               // the mesh of the last nwd_set_mesh and its grid (m.nf == 0: the context holds no mesh)
     bool has_twin = false;
-    double rho_max = 0.0;
-    bq::Grid<double> g;
-    DevBuf mpos, mfaces, mtwin, cen, rho, red, mm, cell, ccount, cstart, sorted, scan_tmp;
+    DevBuf mtwin;
     // nwd_query
     DevBuf up, qmm, dist, closest, face, feature, partial, sum;
 };
@@ -190,19 +157,7 @@ namespace {
 
 #define NWD_HIP(call) BQ_HIP(call, NWD_ERR_NOMEM, NWD_ERR_HIP)
 
-// at most max(16 F, 65536) cells, up to 2^26; at most 1025 an axis; 400 widening steps
-const bq::GridRule NWD_GRID_RULE = {16, 1ll << 26, 1025, 400};
-
-bool twin_ok(const int32_t *twin, int64_t nf)
-{
-    const int64_t nh = 3 * nf;
-    for (int64_t h = 0; h < nh; ++h) {
-        const int32_t t = twin[h];
-        if (t == -1) continue;
-        if (t < 0 || t >= nh || twin[t] != h) return false;
-    }
-    return true;
-}
+const bq::FaceCodes NWD_FACE_CODES = {NWD_ERR_BADARG, NWD_ERR_NONFINITE, NWD_ERR_NOMEM, NWD_ERR_HIP};
 
 }  // namespace
 
@@ -216,48 +171,20 @@ NWD_EXPORT const char *nwd_last_error(nwd_ctx *ctx) { return bq::last_error(ctx)
 
 NWD_EXPORT int nwd_set_mesh(nwd_ctx *ctx, const float *pos, int64_t n_vertices, const int32_t *faces, int64_t n_faces, const int32_t *twin)
 {
-    if (ctx) ctx->nf = 0;
-    if (!pos || !faces || n_vertices < 3 || n_faces < 1 || n_vertices > (1ll << 30) || n_faces > (1ll << 29)) return fail(ctx, NWD_ERR_BADARG, "nwd_set_mesh: a NULL array or a size out of range");
-    if (!bq::all_finite(pos, 3 * n_vertices)) return fail(ctx, NWD_ERR_NONFINITE, "nwd_set_mesh: a vertex position is not finite");
-    if (!bq::mesh_ok(pos, n_vertices, faces, n_faces)) return fail(ctx, NWD_ERR_BADARG, "nwd_set_mesh: a face index outside the vertices");
-    if (twin && !twin_ok(twin, n_faces)) return fail(ctx, NWD_ERR_BADARG, "nwd_set_mesh: the twin table is not -1 or an involution within [0, 3F)");
+    if (ctx) ctx->m.nf = 0;
+    bq::FaceStatus s = bq::check_faces(pos, n_vertices, faces, n_faces);
+    if (!s.ok()) return bq::face_fail(ctx, "nwd_set_mesh", s, NWD_FACE_CODES);
+    if (twin && !bq::twin_ok(twin, n_faces)) return fail(ctx, NWD_ERR_BADARG, "nwd_set_mesh: the twin table is not -1 or an involution within [0, 3F)");
     if (!ctx) return NWD_ERR_BADARG;
     NWD_HIP(hipSetDevice(ctx->device));
-    const int nf = (int)n_faces;
-    NWD_HIP(bq::upload(ctx->stream, ctx->mpos, pos, 3 * n_vertices));
-    NWD_HIP(bq::upload(ctx->stream, ctx->mfaces, faces, 3 * n_faces));
+    bq::FaceGrid &m = ctx->m;
     if (twin) NWD_HIP(bq::upload(ctx->stream, ctx->mtwin, twin, 3 * n_faces));
-    NWD_HIP(ctx->cen.ensure(sizeof(double) * 3 * (size_t)nf));
-    NWD_HIP(ctx->rho.ensure(sizeof(double) * (size_t)nf));
-    NWD_HIP(ctx->red.ensure(sizeof(double) * 2));
-    hipLaunchKernelGGL(k_md_face_setup, dim3(nblk(nf)), dim3(NWD_BLOCK), 0, ctx->stream, ctx->mpos.as<float>(), ctx->mfaces.as<int>(), nf,
-                       ctx->cen.as<double>(), ctx->rho.as<double>());
-    hipLaunchKernelGGL(k_md_rho_reduce, dim3(1), dim3(NWD_BLOCK), 0, ctx->stream, ctx->rho.as<double>(), nf, ctx->red.as<double>());
-    NWD_HIP(hipGetLastError());
-    double red[2] = {0.0, 0.0};
-    NWD_HIP(hipMemcpyAsync(red, ctx->red.p, sizeof(red), hipMemcpyDeviceToHost, ctx->stream));
-    NWD_HIP(hipStreamSynchronize(ctx->stream));                   // (red is a stack array: nothing may be pending on it past this point)
-    bool finite[2];
-    NWD_HIP(bq::bounds<double>(ctx->stream, ctx->mm, ctx->cen.as<double>(), nf, nullptr, 0, &ctx->g, finite));
-    if (!finite[0] || !std::isfinite(red[0]) || !std::isfinite(red[1])) return fail(ctx, NWD_ERR_NONFINITE, "nwd_set_mesh: a face's centroid or radius is not a finite double");
-    bq::Grid<double> &g = ctx->g;
-    double ext[3], emax = 0.0;
-    for (int d = 0; d < 3; ++d) { ext[d] = g.hi[d] - g.lo[d]; emax = std::max(emax, ext[d]); }
-    if (!std::isfinite(emax)) return fail(ctx, NWD_ERR_BADARG, "nwd_set_mesh: the mesh's extent is not a finite double");
-    // cell size: twice the mean rho_f (a face or two per occupied cell of a surface), at least a 1024th of the widest axis (1 for a
-    // mesh without extent); then widened until the grid is within NWD_GRID_RULE
-    g.h = 1.0;
-    if (emax > 0.0) {
-        g.h = std::max(2.0 * red[1] / (double)nf, emax / 1024.0);
-        if (!(g.h > 0.0) || !std::isfinite(g.h)) g.h = emax;
-    }
-    if (!bq::size_grid(NWD_GRID_RULE, nf, ext, &g.h, g.dims)) return fail(ctx, NWD_ERR_BADARG, "nwd_set_mesh: no cell size keeps the grid within its cap");
-    int total = -1;
-    NWD_HIP(bq::build_grid<double>(ctx->stream, ctx->cen.as<double>(), nf, g, ctx->cell, ctx->ccount, ctx->scan_tmp, ctx->cstart, ctx->sorted, &total));
-    if (total != nf) return fail(ctx, NWD_ERR_HIP, "nwd_set_mesh: the cell counts do not add up to the faces");
-    ctx->rho_max = red[0];
+    s = m.set_faces(ctx->stream, pos, n_vertices, faces, n_faces);
+    // cell size: twice the mean rho_f (a face or two per occupied cell of a surface), bq::face_cell's floor, then widened until the grid
+    // is within bq::FACE_GRID_RULE
+    if (s.ok()) s = m.bin(ctx->stream, bq::face_cell(2.0 * m.rho_mean, m.emax()));
+    if (!s.ok()) { m.nf = 0; return bq::face_fail(ctx, "nwd_set_mesh", s, NWD_FACE_CODES); }
     ctx->has_twin = twin != nullptr;
-    ctx->nf = nf;
     return NWD_OK;
 }
 
@@ -266,7 +193,7 @@ NWD_EXPORT int nwd_query(nwd_ctx *ctx, const double *xyz, int64_t n, int flags, 
 {
     if (!xyz || n < 1 || n > (1ll << 30) || (flags & ~(NWD_SIGNED | NWD_RINGS))) return fail(ctx, NWD_ERR_BADARG, "nwd_query: a NULL cloud, a size out of range or an unknown flag");
     if (!ctx) return NWD_ERR_BADARG;
-    if (ctx->nf < 1) return fail(ctx, NWD_ERR_NOMESH, "nwd_query: the context holds no mesh");
+    if (ctx->m.nf < 1) return fail(ctx, NWD_ERR_NOMESH, "nwd_query: the context holds no mesh");
     if ((flags & NWD_SIGNED) && !ctx->has_twin) return fail(ctx, NWD_ERR_BADARG, "nwd_query: NWD_SIGNED needs the twin table that nwd_set_mesh was not given");
     NWD_HIP(hipSetDevice(ctx->device));
     const int nq = (int)n;
@@ -288,9 +215,9 @@ NWD_EXPORT int nwd_query(nwd_ctx *ctx, const double *xyz, int64_t n, int flags, 
     if (feature_out) NWD_HIP(ctx->feature.ensure(sizeof(int) * (size_t)nq));
     NWD_HIP(ctx->partial.ensure(sizeof(double) * (size_t)nb));
     NWD_HIP(ctx->sum.ensure(sizeof(double)));
-    hipLaunchKernelGGL(k_md_query, dim3(nb), dim3(NWD_BLOCK), 0, ctx->stream, dq, nq, ctx->mpos.as<float>(), ctx->mfaces.as<int>(),
-                       ctx->has_twin ? ctx->mtwin.as<int>() : nullptr, ctx->nf, ctx->sorted.as<bq::PtF64>(), ctx->cstart.as<int>(), ctx->rho.as<double>(),
-                       ctx->rho_max, ctx->g, flags, dist_out ? ctx->dist.as<double>() : nullptr, closest_out ? ctx->closest.as<double>() : nullptr,
+    hipLaunchKernelGGL(k_md_query, dim3(nb), dim3(NWD_BLOCK), 0, ctx->stream, dq, nq, ctx->m.mpos.as<float>(), ctx->m.mfaces.as<int>(),
+                       ctx->has_twin ? ctx->mtwin.as<int>() : nullptr, ctx->m.nf, ctx->m.sorted.as<bq::PtF64>(), ctx->m.cstart.as<int>(), ctx->m.rho.as<double>(),
+                       ctx->m.rho_max, ctx->m.g, flags, dist_out ? ctx->dist.as<double>() : nullptr, closest_out ? ctx->closest.as<double>() : nullptr,
                        face_out ? ctx->face.as<int>() : nullptr, feature_out ? ctx->feature.as<int>() : nullptr, ctx->partial.as<double>());
     hipLaunchKernelGGL(k_md_sum_final, dim3(1), dim3(NWD_BLOCK), 0, ctx->stream, ctx->partial.as<double>(), nb, ctx->sum.as<double>());
     NWD_HIP(hipGetLastError());

@@ -29,6 +29,8 @@
 #include <cmath>
 #include <cstdint>
 
+#include "nw_bq_core.h"
+
 #if defined(__HIPCC__)
 #define NWD_HD __host__ __device__ __forceinline__
 #else
@@ -164,16 +166,5 @@ NWD_HD double nwd_sign(const double *p, const double *closest, const double *N)
     return nwd_dot(p[0] - closest[0], p[1] - closest[1], p[2] - closest[2], N[0], N[1], N[2]) < 0.0 ? -1.0 : 1.0;
 }
 
-// the centroid of a face in float64, ((a + b) + c) / 3 per axis, and rho = the largest distance from it to a corner: every point of
-// the face lies within rho of the centroid
-NWD_HD double nwd_face_centroid(const float *a, const float *b, const float *c, double *cen)
-{
-    double rho2 = 0.0;
-    for (int d = 0; d < 3; ++d) cen[d] = (((double)a[d] + (double)b[d]) + (double)c[d]) / 3.0;
-    const float *v[3] = {a, b, c};
-    for (int k = 0; k < 3; ++k) {
-        const double ex = (double)v[k][0] - cen[0], ey = (double)v[k][1] - cen[1], ez = (double)v[k][2] - cen[2];
-        rho2 = fmax(rho2, nwd_dot(ex, ey, ez, ex, ey, ez));
-    }
-    return sqrt(rho2);
-}
+// the centroid of a face in float64 and rho, the largest distance from it to a corner: the face grid's (nw_bq_core.h)
+NWD_HD double nwd_face_centroid(const float *a, const float *b, const float *c, double *cen) { return bq::face_centroid(a, b, c, cen); }

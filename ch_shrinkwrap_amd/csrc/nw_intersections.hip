@@ -1,10 +1,11 @@
 // The self-intersection check of a triangle mesh on the device (MI355X, gfx950): include/nw_intersections.h.
 //
-//   nwx_set_mesh    k_mx_face_setup   one thread per face: the float64 centroid and rho_f, the largest centroid-to-corner distance
-//                                     (nw_intersections_core.h), a hair enlarged so that rounding can only make a bound weaker
-//                   k_mx_rho_reduce   rho_max and the sum of rho_f, one workgroup, a fixed order
-//                   (bq::bounds, bq::size_grid, bq::build_grid)   the query units' shared point grid in double over the centroids;
-//                                     a sorted point carries its face id
+//   nwx_set_mesh    (bq::FaceGrid::set_faces)   the mesh query units' shared intake (nw_bq.h): k_bq_face_setup, one thread per face, the
+//                                     float64 centroid and rho_f, the largest centroid-to-corner distance, a hair enlarged so that
+//                                     rounding can only make a bound weaker; k_bq_rho_reduce, rho_max and the sum of rho_f, one
+//                                     workgroup, a fixed order; bq::bounds, the centroids' box
+//                   (bq::FaceGrid::bin)   the shared point grid in double over the centroids (bq::size_grid, bq::build_grid); a sorted
+//                                     point carries its face id
 //   nwx_find        k_mx_count        one thread per face f: the cells that overlap the box c_f +- (rho_f + rho_max), row by row; a
 //                                     centroid with |c_f - c_g| (1 - slack) - rho_g > rho_f is passed over, every other face g != f gets
 //                                     the pair predicate of nw_intersections_core.h with the smaller id first; count[f] = the faces
@@ -19,8 +20,8 @@
 //                                     centroids it read and those that reached the predicate (then k_mx_totals)
 //   nwx_get_pairs   the list, sorted by (f, g) on the host
 //
-// The scan, the point grid, the device buffer with its staging and the context's scaffolding are the query units' shared ones (nw_bq.h);
-// the starting cell size is the distance unit's (twice the mean rho_f: a face or two per occupied cell) and so are the grid's limits.
+// The scan, the point grid, the face grid, the device buffer with its staging and the context's scaffolding are the query units' shared
+// ones (nw_bq.h); the starting cell size is the distance unit's (twice the mean rho_f: a face or two per occupied cell).
 // All stores are vector stores; no kernel uses scratch (build.py's KERNEL_BUDGETS checks it).
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -37,38 +38,8 @@
 
 #define NWX_EXPORT extern "C" __attribute__((visibility("default")))
 #define NWX_BLOCK 256
-#define NWX_SLACK 1e-9            // relative slack of every bound: far above the rounding of a float64 distance, far below what matters
+#define NWX_SLACK BQ_FACE_RHO_SLACK   // relative slack of every bound: far above the rounding of a float64 distance, far below what matters
 #define NWX_CELL_SLACK 1e-6       // of a cell, added to the box in cell units: far above the rounding of (x - lo) / h below 1025
-
-// ---- set-up ---------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(NWX_BLOCK) void k_mx_face_setup(const float *__restrict__ pos, const int *__restrict__ faces, int nf,
-                                                             double *__restrict__ cen, double *__restrict__ rho)
-{
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= nf) return;
-    nwx_v3 m;
-    const double r = nwx_face_centroid(nwx_load(pos, faces, f), &m);
-    cen[3 * (int64_t)f] = m.x;
-    cen[3 * (int64_t)f + 1] = m.y;
-    cen[3 * (int64_t)f + 2] = m.z;
-    rho[f] = r * (1.0 + NWX_SLACK);
-}
-
-// out[0] = the largest rho, out[1] = their sum
-__global__ __launch_bounds__(NWX_BLOCK) void k_mx_rho_reduce(const double *__restrict__ rho, int nf, double *__restrict__ out)
-{
-    __shared__ double s_m[NWX_BLOCK / 64], s_s[NWX_BLOCK / 64];
-    double m = 0.0, s = 0.0;
-    for (int j = threadIdx.x; j < nf; j += NWX_BLOCK) { m = fmax(m, rho[j]); s += rho[j]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { m = fmax(m, __shfl_xor(m, o, 64)); s += __shfl_xor(s, o, 64); }
-    if ((threadIdx.x & 63) == 0) { s_m[threadIdx.x >> 6] = m; s_s[threadIdx.x >> 6] = s; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        out[0] = fmax(fmax(s_m[0], s_m[1]), fmax(s_m[2], s_m[3]));
-        out[1] = ((s_s[0] + s_s[1]) + s_s[2]) + s_s[3];
-    }
-}
 
 // ---- the walk ---------------------------------------------------------------------------------------------------------------------------
 // the cells [lo, hi] along one axis that a box of half-width w cells around the coordinate x can overlap
@@ -102,7 +73,7 @@ __device__ __forceinline__ void mx_walk(const mx_mesh &m, int f, int *__restrict
     if (MODE == MX_EMIT && slots <= 0) return;
     const nwx_tri F = nwx_load(m.pos, m.faces, f);
     nwx_v3 c;
-    (void)nwx_face_centroid(F, &c);                                  // (the centroid k_mx_face_setup stored, bit for bit)
+    (void)nwx_face_centroid(F, &c);                                  // (the centroid k_bq_face_setup stored, bit for bit: bq::face_centroid both times)
     const double rho_f = m.rho[f];
     const double w = (rho_f + m.rho_max) / m.h;
     int x0, x1, y0, y1, z0, z1;
@@ -189,11 +160,7 @@ using bq::fail;
 using bq::nblk;
 
 struct nwx_ctx : bq::Ctx {
-    // the mesh of the last nwx_set_mesh and its grid
-    int nf = 0;                   // 0: the context holds no mesh
-    double rho_max = 0.0;
-    bq::Grid<double> g;
-    DevBuf mpos, mfaces, cen, rho, red, mm, cell, ccount, cstart, sorted, scan_tmp;
+    bq::FaceGrid m;               // the mesh of the last nwx_set_mesh and its grid (m.nf == 0: the context holds no mesh)
     // nwx_find
     bool has_pairs = false;       // the list of the last nwx_find with NWX_PAIRS is in `pairs`
     int64_t n_pairs = 0;
@@ -205,8 +172,7 @@ namespace {
 
 #define NWX_HIP(call) BQ_HIP(call, NWX_ERR_NOMEM, NWX_ERR_HIP)
 
-// at most max(16 F, 65536) cells, up to 2^26; at most 1025 an axis; 400 widening steps (the distance unit's)
-const bq::GridRule NWX_GRID_RULE = {16, 1ll << 26, 1025, 400};
+const bq::FaceCodes NWX_FACE_CODES = {NWX_ERR_BADARG, NWX_ERR_NONFINITE, NWX_ERR_NOMEM, NWX_ERR_HIP};
 
 }  // namespace
 
@@ -220,45 +186,16 @@ NWX_EXPORT const char *nwx_last_error(nwx_ctx *ctx) { return bq::last_error(ctx)
 
 NWX_EXPORT int nwx_set_mesh(nwx_ctx *ctx, const float *pos, int64_t n_vertices, const int32_t *faces, int64_t n_faces)
 {
-    if (ctx) { ctx->nf = 0; ctx->has_pairs = false; ctx->n_pairs = 0; ctx->stats[0] = ctx->stats[1] = 0; }
-    if (!pos || !faces || n_vertices < 3 || n_faces < 1 || n_vertices > (1ll << 30) || n_faces > (1ll << 29)) return fail(ctx, NWX_ERR_BADARG, "nwx_set_mesh: a NULL array or a size out of range");
-    if (!bq::all_finite(pos, 3 * n_vertices)) return fail(ctx, NWX_ERR_NONFINITE, "nwx_set_mesh: a vertex position is not finite");
-    if (!bq::mesh_ok(pos, n_vertices, faces, n_faces)) return fail(ctx, NWX_ERR_BADARG, "nwx_set_mesh: a face index outside the vertices");
+    if (ctx) { ctx->m.nf = 0; ctx->has_pairs = false; ctx->n_pairs = 0; ctx->stats[0] = ctx->stats[1] = 0; }
+    bq::FaceStatus s = bq::check_faces(pos, n_vertices, faces, n_faces);
+    if (!s.ok()) return bq::face_fail(ctx, "nwx_set_mesh", s, NWX_FACE_CODES);
     if (!ctx) return NWX_ERR_BADARG;
     NWX_HIP(hipSetDevice(ctx->device));
-    const int nf = (int)n_faces;
-    NWX_HIP(bq::upload(ctx->stream, ctx->mpos, pos, 3 * n_vertices));
-    NWX_HIP(bq::upload(ctx->stream, ctx->mfaces, faces, 3 * n_faces));
-    NWX_HIP(ctx->cen.ensure(sizeof(double) * 3 * (size_t)nf));
-    NWX_HIP(ctx->rho.ensure(sizeof(double) * (size_t)nf));
-    NWX_HIP(ctx->red.ensure(sizeof(double) * 2));
-    hipLaunchKernelGGL(k_mx_face_setup, dim3(nblk(nf)), dim3(NWX_BLOCK), 0, ctx->stream, ctx->mpos.as<float>(), ctx->mfaces.as<int>(), nf,
-                       ctx->cen.as<double>(), ctx->rho.as<double>());
-    hipLaunchKernelGGL(k_mx_rho_reduce, dim3(1), dim3(NWX_BLOCK), 0, ctx->stream, ctx->rho.as<double>(), nf, ctx->red.as<double>());
-    NWX_HIP(hipGetLastError());
-    double red[2] = {0.0, 0.0};
-    NWX_HIP(hipMemcpyAsync(red, ctx->red.p, sizeof(red), hipMemcpyDeviceToHost, ctx->stream));
-    NWX_HIP(hipStreamSynchronize(ctx->stream));                   // (red is a stack array, and the caller's arrays are free from here on)
-    bool finite[2];
-    NWX_HIP(bq::bounds<double>(ctx->stream, ctx->mm, ctx->cen.as<double>(), nf, nullptr, 0, &ctx->g, finite));
-    if (!finite[0] || !std::isfinite(red[0]) || !std::isfinite(red[1])) return fail(ctx, NWX_ERR_NONFINITE, "nwx_set_mesh: a face's centroid or radius is not a finite double");
-    bq::Grid<double> &g = ctx->g;
-    double ext[3], emax = 0.0;
-    for (int d = 0; d < 3; ++d) { ext[d] = g.hi[d] - g.lo[d]; emax = std::max(emax, ext[d]); }
-    if (!std::isfinite(emax)) return fail(ctx, NWX_ERR_BADARG, "nwx_set_mesh: the mesh's extent is not a finite double");
-    // cell size: twice the mean rho_f (a face or two per occupied cell of a surface), at least a 1024th of the widest axis (1 for a
-    // mesh without extent); then widened until the grid is within NWX_GRID_RULE
-    g.h = 1.0;
-    if (emax > 0.0) {
-        g.h = std::max(2.0 * red[1] / (double)nf, emax / 1024.0);
-        if (!(g.h > 0.0) || !std::isfinite(g.h)) g.h = emax;
-    }
-    if (!bq::size_grid(NWX_GRID_RULE, nf, ext, &g.h, g.dims)) return fail(ctx, NWX_ERR_BADARG, "nwx_set_mesh: no cell size keeps the grid within its cap");
-    int total = -1;
-    NWX_HIP(bq::build_grid<double>(ctx->stream, ctx->cen.as<double>(), nf, g, ctx->cell, ctx->ccount, ctx->scan_tmp, ctx->cstart, ctx->sorted, &total));
-    if (total != nf) return fail(ctx, NWX_ERR_HIP, "nwx_set_mesh: the cell counts do not add up to the faces");
-    ctx->rho_max = red[0];
-    ctx->nf = nf;
+    bq::FaceGrid &m = ctx->m;
+    s = m.set_faces(ctx->stream, pos, n_vertices, faces, n_faces);
+    // cell size: the distance unit's, twice the mean rho_f with bq::face_cell's floor
+    if (s.ok()) s = m.bin(ctx->stream, bq::face_cell(2.0 * m.rho_mean, m.emax()));
+    if (!s.ok()) { m.nf = 0; return bq::face_fail(ctx, "nwx_set_mesh", s, NWX_FACE_CODES); }
     return NWX_OK;
 }
 
@@ -269,17 +206,18 @@ NWX_EXPORT int nwx_find(nwx_ctx *ctx, int flags, int32_t *count_out, int64_t *n_
     ctx->has_pairs = false;
     ctx->n_pairs = 0;
     ctx->stats[0] = ctx->stats[1] = 0;
-    if (ctx->nf < 1) return fail(ctx, NWX_ERR_NOMESH, "nwx_find: the context holds no mesh");
+    if (ctx->m.nf < 1) return fail(ctx, NWX_ERR_NOMESH, "nwx_find: the context holds no mesh");
     NWX_HIP(hipSetDevice(ctx->device));
-    const int nf = ctx->nf, nb = nblk(nf);
+    const int nf = ctx->m.nf, nb = nblk(nf);
     NWX_HIP(ctx->count.ensure(sizeof(int) * (size_t)nf));
     NWX_HIP(ctx->up.ensure(sizeof(int) * (size_t)nf));
     NWX_HIP(ctx->tot.ensure(sizeof(long long) * 3));
+    const bq::FaceGrid &fg = ctx->m;
     mx_mesh m;
-    m.pos = ctx->mpos.as<float>(); m.faces = ctx->mfaces.as<int>(); m.nf = nf;
-    m.pts = ctx->sorted.as<bq::PtF64>(); m.cstart = ctx->cstart.as<int>(); m.rho = ctx->rho.as<double>();
-    m.rho_max = ctx->rho_max; m.lo0 = ctx->g.lo[0]; m.lo1 = ctx->g.lo[1]; m.lo2 = ctx->g.lo[2]; m.h = ctx->g.h;
-    m.d0 = ctx->g.dims[0]; m.d1 = ctx->g.dims[1]; m.d2 = ctx->g.dims[2];
+    m.pos = fg.mpos.as<float>(); m.faces = fg.mfaces.as<int>(); m.nf = nf;
+    m.pts = fg.sorted.as<bq::PtF64>(); m.cstart = fg.cstart.as<int>(); m.rho = fg.rho.as<double>();
+    m.rho_max = fg.rho_max; m.lo0 = fg.g.lo[0]; m.lo1 = fg.g.lo[1]; m.lo2 = fg.g.lo[2]; m.h = fg.g.h;
+    m.d0 = fg.g.dims[0]; m.d1 = fg.g.dims[1]; m.d2 = fg.g.dims[2];
     long long tot[3] = {0, 0, 0};                                 // pairs, (the sum of count[]), crossed faces
     if (flags & NWX_STATS) {
         long long st[3] = {0, 0, 0};                              // candidates read, candidates tested
@@ -308,7 +246,7 @@ NWX_EXPORT int nwx_find(nwx_ctx *ctx, int flags, int32_t *count_out, int64_t *n_
     if (tot[0] > 0) {
         int total = -1;
         NWX_HIP(ctx->start.ensure(sizeof(int) * ((size_t)nf + 1)));
-        NWX_HIP(bq::scan_total(ctx->stream, ctx->up.as<int>(), nf, ctx->start.as<int>(), ctx->scan_tmp, &total));
+        NWX_HIP(bq::scan_total(ctx->stream, ctx->up.as<int>(), nf, ctx->start.as<int>(), ctx->m.scan_tmp, &total));
         if (total != tot[0]) return fail(ctx, NWX_ERR_HIP, "nwx_find: the scan of the pair counts does not add up");
         NWX_HIP(ctx->pairs.ensure(sizeof(int) * 2 * (size_t)total));
         hipLaunchKernelGGL(k_mx_emit, dim3(nb), dim3(NWX_BLOCK), 0, ctx->stream, m, ctx->up.as<int>(), (const int *)ctx->start.as<int>(), ctx->pairs.as<int>());

@@ -28,12 +28,14 @@
 //           against A.  No plane rejection.  The corners are picked with selects, never from an array indexed at run time.
 //   s >= 2  the pair is not examined (faces that share an edge, or a face with a repeated vertex: the remesher's fold test owns those).
 //
-// The centroid of a face and rho, the largest distance from it to a corner, are nw_distance_core.h's: ((a + b) + c) / 3 per axis, then
+// The centroid of a face and rho, the largest distance from it to a corner, are nw_bq_core.h's: ((a + b) + c) / 3 per axis, then
 // the square root of the largest of the three squared distances.  Two faces can only meet if |c_f - c_g| <= rho_f + rho_g.
 // No HIP header is needed: without a HIP compiler NWX_HD is plain `inline`.
 #pragma once
 #include <cmath>
 #include <cstdint>
+
+#include "nw_bq_core.h"
 
 #if defined(__HIPCC__)
 #define NWX_HD __host__ __device__ __forceinline__
@@ -97,12 +99,13 @@ NWX_HD bool nwx_pair(const nwx_tri &A, const nwx_tri &B)
             (int)nwx_seg_tri(B.a, B.b, A, nA) | (int)nwx_seg_tri(B.b, B.c, A, nA) | (int)nwx_seg_tri(B.c, B.a, A, nA)) != 0;
 }
 
-// the centroid of a face in float64, ((a + b) + c) / 3 per axis, and rho = the largest distance from it to a corner: every point of
-// the face lies within rho of the centroid
+// the centroid of a face in float64 and rho, the largest distance from it to a corner: the face grid's (nw_bq_core.h), on the corners
+// that nwx_load has widened
 NWX_HD double nwx_face_centroid(const nwx_tri &t, nwx_v3 *cen)
 {
-    const nwx_v3 m = nwx_v3{((t.a.x + t.b.x) + t.c.x) / 3.0, ((t.a.y + t.b.y) + t.c.y) / 3.0, ((t.a.z + t.b.z) + t.c.z) / 3.0};
-    const nwx_v3 ea = nwx_sub(t.a, m), eb = nwx_sub(t.b, m), ec = nwx_sub(t.c, m);
-    *cen = m;
-    return sqrt(fmax(fmax(fmax(0.0, nwx_dot(ea, ea)), nwx_dot(eb, eb)), nwx_dot(ec, ec)));
+    const double a[3] = {t.a.x, t.a.y, t.a.z}, b[3] = {t.b.x, t.b.y, t.b.z}, c[3] = {t.c.x, t.c.y, t.c.z};
+    double m[3];
+    const double rho = bq::face_centroid(a, b, c, m);
+    *cen = nwx_v3{m[0], m[1], m[2]};
+    return rho;
 }

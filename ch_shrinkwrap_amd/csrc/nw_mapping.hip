@@ -1,10 +1,11 @@
 // Localizations mapped onto a triangle mesh on the device (MI355X, gfx950): include/nw_mapping.h.
 //
-//   nwl_set_mesh    k_lm_face_setup   one thread per face: the float64 centroid and rho_f (nw_distance_core.h), a hair enlarged, and
+//   nwl_set_mesh    (bq::FaceGrid::set_faces)   the mesh query units' shared intake (nw_bq.h), with this unit's kernel in place of
+//                                     k_bq_face_setup:
+//                   k_lm_face_setup   one thread per face: the float64 centroid and rho_f (bq::face_centroid), a hair enlarged, and
 //                                     floor(A_f 2^20) added to area3 of its three corners (64-bit integer atomics)
-//                   k_lm_rho_reduce   rho_max and the sum of rho_f, one workgroup, a fixed order
-//                   (bq::bounds)      the centroids' box
-//   nwl_map         (bq::size_grid, bq::build_grid)   the centroids binned at the cell size the band asks for, if the grid at hand has another
+//                   (k_bq_rho_reduce, bq::bounds)   rho_max and the sum of rho_f, one workgroup, a fixed order; the centroids' box
+//   nwl_map         (bq::FaceGrid::bin)   the centroids binned at the cell size the band asks for, if the grid at hand has another
 //                   k_lm_map          one lane per localization: the capped ring walk of nw_volume_core.h, the band rule and the weights
 //                                     of nw_mapping_core.h; face, weights, distance, closest point; in band the integer atomics on
 //                                     mass, count and the two limbs of every value column; the block's counters
@@ -43,33 +44,17 @@ __global__ __launch_bounds__(NWL_BLOCK) void k_lm_face_setup(const float *__rest
     const int a = faces[3 * (int64_t)f], b = faces[3 * (int64_t)f + 1], c = faces[3 * (int64_t)f + 2];
     const float *pa = pos + 3 * (int64_t)a, *pb = pos + 3 * (int64_t)b, *pc = pos + 3 * (int64_t)c;
     double m[3];
-    const double r = nwd_face_centroid(pa, pb, pc, m);
+    const double r = nwd_face_centroid(pa, pb, pc, m);             // (bq::face_centroid, the face grid's)
     cen[3 * (int64_t)f] = m[0];
     cen[3 * (int64_t)f + 1] = m[1];
     cen[3 * (int64_t)f + 2] = m[2];
-    rho[f] = r * (1.0 + NWV_CORE_SLACK);
+    rho[f] = r * (1.0 + BQ_FACE_RHO_SLACK);
     uint64_t aq;
     if (!nwl_face_area(pa, pb, pc, &aq)) { flag[0] = 1; return; }
     if (aq) {
         atomicAdd(area3 + a, (u64)aq);
         atomicAdd(area3 + b, (u64)aq);
         atomicAdd(area3 + c, (u64)aq);
-    }
-}
-
-// out[0] = the largest rho, out[1] = their sum
-__global__ __launch_bounds__(NWL_BLOCK) void k_lm_rho_reduce(const double *__restrict__ rho, int nf, double *__restrict__ out)
-{
-    __shared__ double s_m[NWL_BLOCK / 64], s_s[NWL_BLOCK / 64];
-    double m = 0.0, s = 0.0;
-    for (int j = threadIdx.x; j < nf; j += NWL_BLOCK) { m = fmax(m, rho[j]); s += rho[j]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { m = fmax(m, __shfl_xor(m, o, 64)); s += __shfl_xor(s, o, 64); }
-    if ((threadIdx.x & 63) == 0) { s_m[threadIdx.x >> 6] = m; s_s[threadIdx.x >> 6] = s; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        out[0] = fmax(fmax(s_m[0], s_m[1]), fmax(s_m[2], s_m[3]));
-        out[1] = ((s_s[0] + s_s[1]) + s_s[2]) + s_s[3];
     }
 }
 
@@ -181,13 +166,9 @@ using bq::fail;
 using bq::nblk;
 
 struct nwl_ctx : bq::Ctx {
-    // the mesh of the last nwl_set_mesh
-    int nf = 0;                   // 0: the context holds no mesh
-    int64_t nv = 0;
-    double rho_max = 0.0, rho_mean = 0.0;
-    bq::Grid<double> g{};         // lo, hi: the centroids' box; h, dims: the grid at hand
-    double h_start = 0.0;         // the cell size the grid at hand was sized from (0: none)
-    DevBuf mpos, mfaces, cen, rho, red, mm, cell, ccount, cstart, sorted, scan_tmp, area3, flag;
+    bq::FaceGrid m;               // the mesh of the last nwl_set_mesh and the grid at hand (m.nf == 0: the context holds no mesh)
+    DevBuf area3, flag;
+    int flag_h[NWL_FLAG_WORDS] = {0, 0, 0};      // (in the context: nwl_set_mesh's copy into it is queued inside bq::FaceGrid::set_faces)
     // nwl_map
     DevBuf up, upv, scales, qmm, face, w, dist, closest, mass, count, sum_hi, sum_lo, partial, totals;
     int acc_columns = -1;         // the columns of the accumulators at hand (-1: none to add onto)
@@ -198,39 +179,23 @@ namespace {
 
 #define NWL_HIP(call) BQ_HIP(call, NWL_ERR_NOMEM, NWL_ERR_HIP)
 
-// at most max(16 F, 65536) cells, up to 2^26; at most 1025 an axis; 400 widening steps (nwd_'s rule)
-const bq::GridRule NWL_GRID_RULE = {16, 1ll << 26, 1025, 400};
+const bq::FaceCodes NWL_FACE_CODES = {NWL_ERR_BADARG, NWL_ERR_NONFINITE, NWL_ERR_NOMEM, NWL_ERR_HIP};
 const double NWL_MAX_CAP = 1099511627776.0;           // 2^40
 const int64_t NWL_MAX_N = 1ll << 30;
 
-// the cell size a band starts from, the volume unit's rule: twice the mean rho_f (a face or two per occupied cell of a surface) or half
-// of d_cap + rho_max, whichever is larger -- a far localization then ends its walk after three or four rings -- and at least a 1024th
-// of the widest axis; 1 for a mesh without extent
-double starting_cell(const nwl_ctx *ctx, double d_cap)
+// bq::FaceGrid::set_faces' set-up step: the vertex areas and the flag words cleared, k_lm_face_setup, and the flag words on their way
+// back; set_faces synchronises the stream before it returns
+hipError_t face_setup_with_areas(void *user, hipStream_t stream, const float *pos, int64_t n_vertices, const int *faces, int nf, double *cen, double *rho)
 {
-    double emax = 0.0;
-    for (int d = 0; d < 3; ++d) emax = std::max(emax, ctx->g.hi[d] - ctx->g.lo[d]);
-    if (!(emax > 0.0)) return 1.0;
-    double h = std::max(std::max(2.0 * ctx->rho_mean, (d_cap + ctx->rho_max) / 2.0), emax / 1024.0);
-    if (!(h > 0.0) || !std::isfinite(h)) h = emax;
-    return h;
-}
-
-// the grid for this band: the one at hand if it was sized from the same starting cell, else the centroids binned anew
-int ensure_grid(nwl_ctx *ctx, double d_cap)
-{
-    const double h0 = starting_cell(ctx, d_cap);
-    if (ctx->h_start == h0) return NWL_OK;
-    ctx->h_start = 0.0;
-    double ext[3];
-    for (int d = 0; d < 3; ++d) ext[d] = ctx->g.hi[d] - ctx->g.lo[d];
-    ctx->g.h = h0;
-    if (!bq::size_grid(NWL_GRID_RULE, ctx->nf, ext, &ctx->g.h, ctx->g.dims)) return fail(ctx, NWL_ERR_BADARG, "nwl_map: no cell size keeps the grid within its cap");
-    int total = -1;
-    NWL_HIP(bq::build_grid<double>(ctx->stream, ctx->cen.as<double>(), ctx->nf, ctx->g, ctx->cell, ctx->ccount, ctx->scan_tmp, ctx->cstart, ctx->sorted, &total));
-    if (total != ctx->nf) return fail(ctx, NWL_ERR_HIP, "nwl_map: the cell counts do not add up to the faces");
-    ctx->h_start = h0;
-    return NWL_OK;
+    nwl_ctx *ctx = (nwl_ctx *)user;
+    const size_t nv = (size_t)n_vertices;
+    BQ_TRY(ctx->area3.ensure(sizeof(uint64_t) * nv));
+    BQ_TRY(ctx->flag.ensure(sizeof(int) * NWL_FLAG_WORDS));
+    BQ_TRY(hipMemsetAsync(ctx->area3.p, 0, sizeof(uint64_t) * nv, stream));
+    BQ_TRY(hipMemsetAsync(ctx->flag.p, 0, sizeof(int) * NWL_FLAG_WORDS, stream));
+    hipLaunchKernelGGL(k_lm_face_setup, dim3(nblk(nf)), dim3(NWL_BLOCK), 0, stream, pos, faces, nf, cen, rho, ctx->area3.as<u64>(), ctx->flag.as<int>());
+    BQ_TRY(hipGetLastError());
+    return hipMemcpyAsync(ctx->flag_h, ctx->flag.p, sizeof(ctx->flag_h), hipMemcpyDeviceToHost, stream);
 }
 
 bool power_of_two(double s)
@@ -251,42 +216,15 @@ NWL_EXPORT const char *nwl_last_error(nwl_ctx *ctx) { return bq::last_error(ctx)
 
 NWL_EXPORT int nwl_set_mesh(nwl_ctx *ctx, const float *pos, int64_t n_vertices, const int32_t *faces, int64_t n_faces)
 {
-    if (ctx) { ctx->nf = 0; ctx->nv = 0; ctx->h_start = 0.0; ctx->acc_columns = -1; ctx->acc_n = 0; }
-    if (!pos || !faces || n_vertices < 3 || n_faces < 1 || n_vertices > (1ll << 30) || n_faces > (1ll << 29)) return fail(ctx, NWL_ERR_BADARG, "nwl_set_mesh: a NULL array or a size out of range");
-    if (!bq::all_finite(pos, 3 * n_vertices)) return fail(ctx, NWL_ERR_NONFINITE, "nwl_set_mesh: a vertex position is not finite");
-    if (!bq::mesh_ok(pos, n_vertices, faces, n_faces)) return fail(ctx, NWL_ERR_BADARG, "nwl_set_mesh: a face index outside the vertices");
+    if (ctx) { ctx->m.nf = 0; ctx->acc_columns = -1; ctx->acc_n = 0; }
+    bq::FaceStatus s = bq::check_faces(pos, n_vertices, faces, n_faces);
+    if (!s.ok()) return bq::face_fail(ctx, "nwl_set_mesh", s, NWL_FACE_CODES);
     if (!ctx) return NWL_ERR_BADARG;
     NWL_HIP(hipSetDevice(ctx->device));
-    const int nf = (int)n_faces;
-    NWL_HIP(bq::upload(ctx->stream, ctx->mpos, pos, 3 * n_vertices));
-    NWL_HIP(bq::upload(ctx->stream, ctx->mfaces, faces, 3 * n_faces));
-    NWL_HIP(ctx->cen.ensure(sizeof(double) * 3 * (size_t)nf));
-    NWL_HIP(ctx->rho.ensure(sizeof(double) * (size_t)nf));
-    NWL_HIP(ctx->red.ensure(sizeof(double) * 2));
-    NWL_HIP(ctx->area3.ensure(sizeof(uint64_t) * (size_t)n_vertices));
-    NWL_HIP(ctx->flag.ensure(sizeof(int) * NWL_FLAG_WORDS));
-    NWL_HIP(hipMemsetAsync(ctx->area3.p, 0, sizeof(uint64_t) * (size_t)n_vertices, ctx->stream));
-    NWL_HIP(hipMemsetAsync(ctx->flag.p, 0, sizeof(int) * NWL_FLAG_WORDS, ctx->stream));
-    hipLaunchKernelGGL(k_lm_face_setup, dim3(nblk(nf)), dim3(NWL_BLOCK), 0, ctx->stream, ctx->mpos.as<float>(), ctx->mfaces.as<int>(), nf,
-                       ctx->cen.as<double>(), ctx->rho.as<double>(), ctx->area3.as<u64>(), ctx->flag.as<int>());
-    hipLaunchKernelGGL(k_lm_rho_reduce, dim3(1), dim3(NWL_BLOCK), 0, ctx->stream, ctx->rho.as<double>(), nf, ctx->red.as<double>());
-    NWL_HIP(hipGetLastError());
-    double red[2] = {0.0, 0.0};
-    int flag[NWL_FLAG_WORDS] = {0, 0, 0};
-    NWL_HIP(hipMemcpyAsync(red, ctx->red.p, sizeof(red), hipMemcpyDeviceToHost, ctx->stream));
-    NWL_HIP(hipMemcpyAsync(flag, ctx->flag.p, sizeof(flag), hipMemcpyDeviceToHost, ctx->stream));
-    NWL_HIP(hipStreamSynchronize(ctx->stream));                   // (red and flag are stack arrays, and the uploads' sources are the caller's)
-    bool finite[2];
-    NWL_HIP(bq::bounds<double>(ctx->stream, ctx->mm, ctx->cen.as<double>(), nf, nullptr, 0, &ctx->g, finite));
-    if (!finite[0] || !std::isfinite(red[0]) || !std::isfinite(red[1])) return fail(ctx, NWL_ERR_NONFINITE, "nwl_set_mesh: a face's centroid or radius is not a finite double");
-    if (flag[0]) return fail(ctx, NWL_ERR_BADARG, "nwl_set_mesh: a face of area 2^40 or more");
-    double emax = 0.0;
-    for (int d = 0; d < 3; ++d) emax = std::max(emax, ctx->g.hi[d] - ctx->g.lo[d]);
-    if (!std::isfinite(emax)) return fail(ctx, NWL_ERR_BADARG, "nwl_set_mesh: the mesh's extent is not a finite double");
-    ctx->rho_max = red[0];
-    ctx->rho_mean = red[1] / (double)nf;
-    ctx->nv = n_vertices;
-    ctx->nf = nf;
+    s = ctx->m.set_faces(ctx->stream, pos, n_vertices, faces, n_faces, face_setup_with_areas, ctx);
+    if (!s.ok()) return bq::face_fail(ctx, "nwl_set_mesh", s, NWL_FACE_CODES);
+    // (after set_faces' own checks, of which only the non-finite centroid can fail: the extent of finite centroids of float32 corners is finite)
+    if (ctx->flag_h[0]) { ctx->m.nf = 0; return fail(ctx, NWL_ERR_BADARG, "nwl_set_mesh: a face of area 2^40 or more"); }
     return NWL_OK;
 }
 
@@ -294,9 +232,9 @@ NWL_EXPORT int nwl_get_areas(nwl_ctx *ctx, uint64_t *area3_out)
 {
     if (!area3_out) return fail(ctx, NWL_ERR_BADARG, "nwl_get_areas: a NULL array");
     if (!ctx) return NWL_ERR_BADARG;
-    if (ctx->nf < 1) return fail(ctx, NWL_ERR_NOMESH, "nwl_get_areas: the context holds no mesh");
+    if (ctx->m.nf < 1) return fail(ctx, NWL_ERR_NOMESH, "nwl_get_areas: the context holds no mesh");
     NWL_HIP(hipSetDevice(ctx->device));
-    NWL_HIP(hipMemcpyAsync(area3_out, ctx->area3.p, sizeof(uint64_t) * (size_t)ctx->nv, hipMemcpyDeviceToHost, ctx->stream));
+    NWL_HIP(hipMemcpyAsync(area3_out, ctx->area3.p, sizeof(uint64_t) * (size_t)ctx->m.nv, hipMemcpyDeviceToHost, ctx->stream));
     NWL_HIP(hipStreamSynchronize(ctx->stream));
     return NWL_OK;
 }
@@ -315,7 +253,7 @@ NWL_EXPORT int nwl_map(nwl_ctx *ctx, const double *xyz, int64_t n, const double 
         if (!power_of_two(scales[c])) return fail(ctx, NWL_ERR_BADARG, "nwl_map: a scale that is not a power of two within [2^-900, 2^899]");
     if (!std::isfinite(d_cap) || !(d_cap > 0.0) || !(d_cap <= NWL_MAX_CAP)) return fail(ctx, NWL_ERR_BADARG, "nwl_map: the band must be finite and within (0, 2^40]");
     if (!ctx) return NWL_ERR_BADARG;
-    if (ctx->nf < 1) return fail(ctx, NWL_ERR_NOMESH, "nwl_map: the context holds no mesh");
+    if (ctx->m.nf < 1) return fail(ctx, NWL_ERR_NOMESH, "nwl_map: the context holds no mesh");
     if (accumulate && keep_columns != n_columns) return fail(ctx, NWL_ERR_BADARG, "nwl_map: NWL_ACCUMULATE needs the accumulators of a call with the same mesh and the same number of columns");
     if (accumulate && keep_n + n > NWL_MAX_N) return fail(ctx, NWL_ERR_BADARG, "nwl_map: more than 2^30 localizations in one set of accumulators");
     NWL_HIP(hipSetDevice(ctx->device));
@@ -339,10 +277,12 @@ NWL_EXPORT int nwl_map(nwl_ctx *ctx, const double *xyz, int64_t n, const double 
         }
         NWL_HIP(bq::upload(ctx->stream, ctx->scales, scales, n_columns));
     }
-    const int r = ensure_grid(ctx, d_cap);
-    if (r != NWL_OK) return r;
+    bq::FaceGrid &m = ctx->m;
+    // the grid for this band, the volume unit's rule: from the cell size bq::band_cell and bq::face_cell give
+    const bq::FaceStatus s = m.bin(ctx->stream, bq::face_cell(bq::band_cell(m.rho_mean, m.rho_max, d_cap), m.emax()));
+    if (!s.ok()) return bq::face_fail(ctx, "nwl_map", s, NWL_FACE_CODES);
     const int nb = nblk(n, NWL_BLOCK);
-    const size_t nv = (size_t)ctx->nv, nf = (size_t)ctx->nf, nvc = std::max<size_t>(nv * (size_t)n_columns, 1);
+    const size_t nv = (size_t)m.nv, nf = (size_t)m.nf, nvc = std::max<size_t>(nv * (size_t)n_columns, 1);
     if (face_out) NWL_HIP(ctx->face.ensure(sizeof(int) * (size_t)n));
     if (w_out) NWL_HIP(ctx->w.ensure(sizeof(int) * 3 * (size_t)n));
     if (dist_out) NWL_HIP(ctx->dist.ensure(sizeof(double) * (size_t)n));
@@ -368,11 +308,11 @@ NWL_EXPORT int nwl_map(nwl_ctx *ctx, const double *xyz, int64_t n, const double 
         }
     }
     nwv_grid g;
-    for (int d = 0; d < 3; ++d) { g.lo[d] = ctx->g.lo[d]; g.hi[d] = ctx->g.hi[d]; g.dims[d] = ctx->g.dims[d]; }
-    g.h = ctx->g.h;
+    for (int d = 0; d < 3; ++d) { g.lo[d] = m.g.lo[d]; g.hi[d] = m.g.hi[d]; g.dims[d] = m.g.dims[d]; }
+    g.h = m.g.h;
     hipLaunchKernelGGL(k_lm_map, dim3(nb), dim3(NWL_BLOCK), 0, ctx->stream, dq, n, dv, walk_only ? 0 : n_columns, ctx->scales.as<double>(),
-                       ctx->mpos.as<float>(), ctx->mfaces.as<int>(), ctx->nf, ctx->sorted.as<nwv_pt>(), ctx->cstart.as<int>(), ctx->rho.as<double>(),
-                       ctx->rho_max, g, d_cap, face_out ? ctx->face.as<int>() : nullptr, w_out ? ctx->w.as<int>() : nullptr,
+                       m.mpos.as<float>(), m.mfaces.as<int>(), m.nf, m.sorted.as<nwv_pt>(), m.cstart.as<int>(), m.rho.as<double>(),
+                       m.rho_max, g, d_cap, face_out ? ctx->face.as<int>() : nullptr, w_out ? ctx->w.as<int>() : nullptr,
                        dist_out ? ctx->dist.as<double>() : nullptr, closest_out ? ctx->closest.as<double>() : nullptr,
                        walk_only ? nullptr : ctx->mass.as<u64>(), ctx->count.as<int>(), ctx->sum_hi.as<u64>(), ctx->sum_lo.as<u64>(), ctx->flag.as<int>(),
                        ctx->partial.as<long long>());
@@ -400,8 +340,8 @@ NWL_EXPORT int nwl_map(nwl_ctx *ctx, const double *xyz, int64_t n, const double 
         info_out[NWL_INFO_IN_BAND] = tot[0];
         info_out[NWL_INFO_RINGS] = tot[1];
         info_out[NWL_INFO_CENTROIDS] = tot[2];
-        info_out[NWL_INFO_CELLS] = ctx->g.cells();
-        info_out[NWL_INFO_CELL_SIZE] = __builtin_bit_cast(int64_t, ctx->g.h);
+        info_out[NWL_INFO_CELLS] = m.g.cells();
+        info_out[NWL_INFO_CELL_SIZE] = __builtin_bit_cast(int64_t, m.g.h);
     }
     if (walk_only) return NWL_OK;                                 // (the accumulators at hand are as they were)
     ctx->acc_columns = n_columns;

@@ -63,7 +63,7 @@
 #else
 #define NWM_KEEP_LOOP
 #endif
-#define NWM_CORE_SLACK 1e-9       // relative slack of every bound: far above the rounding of a float64 distance, far below what matters
+#define NWM_CORE_SLACK BQ_FACE_RHO_SLACK      // (nw_bq_core.h: 1e-9) relative slack of every bound: far above the rounding of a float64 distance, far below what matters
 
 // the centroid grid as the walk reads it (the layout of the query units' shared grid in double) and a sorted centroid with its face id
 struct nwm_grid {
@@ -77,6 +77,15 @@ struct nwm_best {
     double d2;                // the best squared distance
     int face;
 };
+
+// The candidate cell size of a band d_cap (bq::face_cell takes it from there): max(2 m, min((d_cap + rho_max) / 2, 16 m)) with m the
+// mean rho of B.  2 m is a face or two per occupied cell of a surface; half of d_cap + rho_max ends a far face's walk after three or
+// four rings; 16 m is where a walk without a band was fastest when it was measured (profiles/proximity.txt: its rings cost more than
+// the centroids a larger cell makes it read), and it keeps a wide band from turning the grid into a few cells that hold every centroid.
+inline double nwm_band_cell(double rho_mean, double rho_max, double d_cap)
+{
+    return std::max(2.0 * rho_mean, std::min((d_cap + rho_max) / 2.0, 16.0 * rho_mean));
+}
 
 NWD_HD bool nwm_in_band(double u, double d_cap) { return u <= d_cap; }
 

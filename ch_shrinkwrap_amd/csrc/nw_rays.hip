@@ -1,10 +1,11 @@
 // Exact ray casting against a triangle mesh on the device (MI355X, gfx950): include/nw_rays.h.
 //
-//   nwc_set_mesh    k_rc_face_setup   one thread per face: the float64 centroid and rho_f, the largest centroid-to-corner distance
-//                                     (nw_intersections_core.h), a hair enlarged so that rounding can only make a bound weaker
-//                   k_rc_rho_reduce   rho_max and the sum of rho_f, one workgroup, a fixed order
-//                   (bq::bounds, bq::size_grid, bq::build_grid)   the query units' shared point grid in double over the centroids;
-//                                     a sorted point carries its face id
+//   nwc_set_mesh    (bq::FaceGrid::set_faces)   the mesh query units' shared intake (nw_bq.h): k_bq_face_setup, one thread per face, the
+//                                     float64 centroid and rho_f, the largest centroid-to-corner distance, a hair enlarged so that
+//                                     rounding can only make a bound weaker; k_bq_rho_reduce, rho_max and the sum of rho_f, one
+//                                     workgroup, a fixed order; bq::bounds, the centroids' box
+//                   (bq::FaceGrid::bin)   the shared point grid in double over the centroids (bq::size_grid, bq::build_grid); a sorted
+//                                     point carries its face id
 //   nwc_cast        k_rc_first        one lane per ray, nw_rays_core.h's walk: the ray clipped against the centroids' box dilated by
 //                                     rho_max, its arc length inside cut into pieces of one cell size, per piece the cells that overlap
 //                                     a box around its midpoint, row by row; a centroid whose arc coordinate falls into the piece and
@@ -13,8 +14,8 @@
 //                   k_rc_count        the same walk to its end: the number of faces hit as well (NWC_COUNT)
 //                   k_rc_totals       with NWC_STATS: the sums of the lanes' three counters, one workgroup, integers
 //
-// The point grid, the device buffer with its staging and the context's scaffolding are the query units' shared ones (nw_bq.h); the
-// starting cell size is the distance unit's (twice the mean rho_f: a face or two per occupied cell) and so are the grid's limits.
+// The point grid, the face grid, the device buffer with its staging and the context's scaffolding are the query units' shared ones
+// (nw_bq.h); the starting cell size is the distance unit's (twice the mean rho_f: a face or two per occupied cell).
 // All stores are vector stores in plain C++; no kernel uses scratch (build.py's KERNEL_BUDGETS checks it).
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -31,36 +32,6 @@
 #define NWC_BLOCK 256
 
 static_assert(sizeof(nwc_point) == sizeof(bq::PtF64) && offsetof(nwc_point, i) == offsetof(bq::PtF64, i), "nwc_point is bq::PtF64");
-
-// ---- set-up ---------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(NWC_BLOCK) void k_rc_face_setup(const float *__restrict__ pos, const int *__restrict__ faces, int nf,
-                                                             double *__restrict__ cen, double *__restrict__ rho)
-{
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= nf) return;
-    nwx_v3 m;
-    const double r = nwx_face_centroid(nwx_load(pos, faces, f), &m);
-    cen[3 * (int64_t)f] = m.x;
-    cen[3 * (int64_t)f + 1] = m.y;
-    cen[3 * (int64_t)f + 2] = m.z;
-    rho[f] = r * (1.0 + NWC_RHO_SLACK);
-}
-
-// out[0] = the largest rho, out[1] = their sum
-__global__ __launch_bounds__(NWC_BLOCK) void k_rc_rho_reduce(const double *__restrict__ rho, int nf, double *__restrict__ out)
-{
-    __shared__ double s_m[NWC_BLOCK / 64], s_s[NWC_BLOCK / 64];
-    double m = 0.0, s = 0.0;
-    for (int j = threadIdx.x; j < nf; j += NWC_BLOCK) { m = fmax(m, rho[j]); s += rho[j]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { m = fmax(m, __shfl_xor(m, o, 64)); s += __shfl_xor(s, o, 64); }
-    if ((threadIdx.x & 63) == 0) { s_m[threadIdx.x >> 6] = m; s_s[threadIdx.x >> 6] = s; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        out[0] = fmax(fmax(s_m[0], s_m[1]), fmax(s_m[2], s_m[3]));
-        out[1] = ((s_s[0] + s_s[1]) + s_s[2]) + s_s[3];
-    }
-}
 
 // ---- the cast ---------------------------------------------------------------------------------------------------------------------------
 struct rc_rays {
@@ -120,11 +91,7 @@ using bq::fail;
 using bq::nblk;
 
 struct nwc_ctx : bq::Ctx {
-    // the mesh of the last nwc_set_mesh and its grid
-    int nf = 0;                   // 0: the context holds no mesh
-    double rho_max = 0.0;
-    bq::Grid<double> g;
-    DevBuf mpos, mfaces, cen, rho, red, mm, cell, ccount, cstart, sorted, scan_tmp;
+    bq::FaceGrid m;               // the mesh of the last nwc_set_mesh and its grid (m.nf == 0: the context holds no mesh)
     // nwc_cast
     int64_t stats[3] = {0, 0, 0};
     long long tot_h[3] = {0, 0, 0};
@@ -135,8 +102,7 @@ namespace {
 
 #define NWC_HIP(call) BQ_HIP(call, NWC_ERR_NOMEM, NWC_ERR_HIP)
 
-// at most max(16 F, 65536) cells, up to 2^26; at most 1025 an axis; 400 widening steps (the distance unit's)
-const bq::GridRule NWC_GRID_RULE = {16, 1ll << 26, 1025, 400};
+const bq::FaceCodes NWC_FACE_CODES = {NWC_ERR_BADARG, NWC_ERR_NONFINITE, NWC_ERR_NOMEM, NWC_ERR_HIP};
 
 }  // namespace
 
@@ -150,45 +116,16 @@ NWC_EXPORT const char *nwc_last_error(nwc_ctx *ctx) { return bq::last_error(ctx)
 
 NWC_EXPORT int nwc_set_mesh(nwc_ctx *ctx, const float *pos, int64_t n_vertices, const int32_t *faces, int64_t n_faces)
 {
-    if (ctx) { ctx->nf = 0; ctx->stats[0] = ctx->stats[1] = ctx->stats[2] = 0; }
-    if (!pos || !faces || n_vertices < 3 || n_faces < 1 || n_vertices > (1ll << 30) || n_faces > (1ll << 29)) return fail(ctx, NWC_ERR_BADARG, "nwc_set_mesh: a NULL array or a size out of range");
-    if (!bq::all_finite(pos, 3 * n_vertices)) return fail(ctx, NWC_ERR_NONFINITE, "nwc_set_mesh: a vertex position is not finite");
-    if (!bq::mesh_ok(pos, n_vertices, faces, n_faces)) return fail(ctx, NWC_ERR_BADARG, "nwc_set_mesh: a face index outside the vertices");
+    if (ctx) { ctx->m.nf = 0; ctx->stats[0] = ctx->stats[1] = ctx->stats[2] = 0; }
+    bq::FaceStatus s = bq::check_faces(pos, n_vertices, faces, n_faces);
+    if (!s.ok()) return bq::face_fail(ctx, "nwc_set_mesh", s, NWC_FACE_CODES);
     if (!ctx) return NWC_ERR_BADARG;
     NWC_HIP(hipSetDevice(ctx->device));
-    const int nf = (int)n_faces;
-    NWC_HIP(bq::upload(ctx->stream, ctx->mpos, pos, 3 * n_vertices));
-    NWC_HIP(bq::upload(ctx->stream, ctx->mfaces, faces, 3 * n_faces));
-    NWC_HIP(ctx->cen.ensure(sizeof(double) * 3 * (size_t)nf));
-    NWC_HIP(ctx->rho.ensure(sizeof(double) * (size_t)nf));
-    NWC_HIP(ctx->red.ensure(sizeof(double) * 2));
-    hipLaunchKernelGGL(k_rc_face_setup, dim3(nblk(nf)), dim3(NWC_BLOCK), 0, ctx->stream, ctx->mpos.as<float>(), ctx->mfaces.as<int>(), nf,
-                       ctx->cen.as<double>(), ctx->rho.as<double>());
-    hipLaunchKernelGGL(k_rc_rho_reduce, dim3(1), dim3(NWC_BLOCK), 0, ctx->stream, ctx->rho.as<double>(), nf, ctx->red.as<double>());
-    NWC_HIP(hipGetLastError());
-    double red[2] = {0.0, 0.0};
-    NWC_HIP(hipMemcpyAsync(red, ctx->red.p, sizeof(red), hipMemcpyDeviceToHost, ctx->stream));
-    NWC_HIP(hipStreamSynchronize(ctx->stream));                   // (red is a stack array, and the caller's arrays are free from here on)
-    bool finite[2];
-    NWC_HIP(bq::bounds<double>(ctx->stream, ctx->mm, ctx->cen.as<double>(), nf, nullptr, 0, &ctx->g, finite));
-    if (!finite[0] || !std::isfinite(red[0]) || !std::isfinite(red[1])) return fail(ctx, NWC_ERR_NONFINITE, "nwc_set_mesh: a face's centroid or radius is not a finite double");
-    bq::Grid<double> &g = ctx->g;
-    double ext[3], emax = 0.0;
-    for (int d = 0; d < 3; ++d) { ext[d] = g.hi[d] - g.lo[d]; emax = std::max(emax, ext[d]); }
-    if (!std::isfinite(emax)) return fail(ctx, NWC_ERR_BADARG, "nwc_set_mesh: the mesh's extent is not a finite double");
-    // cell size: twice the mean rho_f (a face or two per occupied cell of a surface), at least a 1024th of the widest axis (1 for a
-    // mesh without extent); then widened until the grid is within NWC_GRID_RULE
-    g.h = 1.0;
-    if (emax > 0.0) {
-        g.h = std::max(2.0 * red[1] / (double)nf, emax / 1024.0);
-        if (!(g.h > 0.0) || !std::isfinite(g.h)) g.h = emax;
-    }
-    if (!bq::size_grid(NWC_GRID_RULE, nf, ext, &g.h, g.dims)) return fail(ctx, NWC_ERR_BADARG, "nwc_set_mesh: no cell size keeps the grid within its cap");
-    int total = -1;
-    NWC_HIP(bq::build_grid<double>(ctx->stream, ctx->cen.as<double>(), nf, g, ctx->cell, ctx->ccount, ctx->scan_tmp, ctx->cstart, ctx->sorted, &total));
-    if (total != nf) return fail(ctx, NWC_ERR_HIP, "nwc_set_mesh: the cell counts do not add up to the faces");
-    ctx->rho_max = red[0];
-    ctx->nf = nf;
+    bq::FaceGrid &m = ctx->m;
+    s = m.set_faces(ctx->stream, pos, n_vertices, faces, n_faces);
+    // cell size: the distance unit's, twice the mean rho_f with bq::face_cell's floor
+    if (s.ok()) s = m.bin(ctx->stream, bq::face_cell(2.0 * m.rho_mean, m.emax()));
+    if (!s.ok()) { m.nf = 0; return bq::face_fail(ctx, "nwc_set_mesh", s, NWC_FACE_CODES); }
     return NWC_OK;
 }
 
@@ -252,13 +189,14 @@ int cast_checked(nwc_ctx *ctx, const rc_args &a)
     if (a.up_d) { NWC_HIP(bq::upload(ctx->stream, ctx->up_d, a.dir, 3 * (int64_t)nq)); q.dir = ctx->up_d.as<double>(); }
     if (a.up_sv) { NWC_HIP(bq::upload(ctx->stream, ctx->up_sv, a.skip_vertex, (int64_t)nq)); q.skip_vertex = ctx->up_sv.as<int>(); }
     if (a.up_sf) { NWC_HIP(bq::upload(ctx->stream, ctx->up_sf, a.skip_face, (int64_t)nq)); q.skip_face = ctx->up_sf.as<int>(); }
+    const bq::FaceGrid &fg = ctx->m;
     nwc_mesh m;
-    m.pos = ctx->mpos.as<float>(); m.faces = ctx->mfaces.as<int>(); m.nf = ctx->nf;
-    m.pts = ctx->sorted.as<nwc_point>(); m.cstart = ctx->cstart.as<int>(); m.rho = ctx->rho.as<double>();
-    m.rho_max = ctx->rho_max; m.h = ctx->g.h;
-    m.lo0 = ctx->g.lo[0]; m.lo1 = ctx->g.lo[1]; m.lo2 = ctx->g.lo[2];
-    m.hi0 = ctx->g.hi[0]; m.hi1 = ctx->g.hi[1]; m.hi2 = ctx->g.hi[2];
-    m.d0 = ctx->g.dims[0]; m.d1 = ctx->g.dims[1]; m.d2 = ctx->g.dims[2];
+    m.pos = fg.mpos.as<float>(); m.faces = fg.mfaces.as<int>(); m.nf = fg.nf;
+    m.pts = fg.sorted.as<nwc_point>(); m.cstart = fg.cstart.as<int>(); m.rho = fg.rho.as<double>();
+    m.rho_max = fg.rho_max; m.h = fg.g.h;
+    m.lo0 = fg.g.lo[0]; m.lo1 = fg.g.lo[1]; m.lo2 = fg.g.lo[2];
+    m.hi0 = fg.g.hi[0]; m.hi1 = fg.g.hi[1]; m.hi2 = fg.g.hi[2];
+    m.d0 = fg.g.dims[0]; m.d1 = fg.g.dims[1]; m.d2 = fg.g.dims[2];
     if (a.flags & NWC_COUNT) hipLaunchKernelGGL(k_rc_count, dim3(nblk(nq)), dim3(NWC_BLOCK), 0, ctx->stream, m, q, out);
     else hipLaunchKernelGGL(k_rc_first, dim3(nblk(nq)), dim3(NWC_BLOCK), 0, ctx->stream, m, q, out);
     if (a.flags & NWC_STATS) hipLaunchKernelGGL(k_rc_totals, dim3(1), dim3(NWC_BLOCK), 0, ctx->stream, (const long long *)out.stats, nq, ctx->tot.as<long long>());
@@ -285,7 +223,7 @@ NWC_EXPORT int nwc_cast(nwc_ctx *ctx, const double *origin, const double *dir, i
     if (!(t_max >= 0.0)) return fail(ctx, NWC_ERR_BADARG, "nwc_cast: t_max is negative or not a number");
     if (hits_out && !(flags & NWC_COUNT)) return fail(ctx, NWC_ERR_BADARG, "nwc_cast: hits_out needs NWC_COUNT");
     if (!ctx) return NWC_ERR_BADARG;
-    if (ctx->nf < 1) return fail(ctx, NWC_ERR_NOMESH, "nwc_cast: the context holds no mesh");
+    if (ctx->m.nf < 1) return fail(ctx, NWC_ERR_NOMESH, "nwc_cast: the context holds no mesh");
     NWC_HIP(hipSetDevice(ctx->device));
     // every check of the rays comes before the first upload of any of them
     rc_args a;
@@ -300,8 +238,8 @@ NWC_EXPORT int nwc_cast(nwc_ctx *ctx, const double *origin, const double *dir, i
     // the walk's allowance for rounding grows with the coordinates (nw_rays_core.h: E); beyond a cell it would make every piece read
     // the whole grid, so such a ray is refused rather than walked for minutes.  (A direction needs no such limit: the walk follows it
     // scaled by its largest component, and its length bounds nothing.)
-    for (int k = 0; k < 3; ++k) gmax = std::max(gmax, std::max(std::fabs(ctx->g.lo[k]), std::fabs(ctx->g.hi[k])));
-    if (!(NWC_REL_SLACK * (omax + gmax) <= ctx->g.h)) return fail(ctx, NWC_ERR_BADARG, "nwc_cast: an origin lies more than 1e9 cells from the origin of the coordinates");
+    for (int k = 0; k < 3; ++k) gmax = std::max(gmax, std::max(std::fabs(ctx->m.g.lo[k]), std::fabs(ctx->m.g.hi[k])));
+    if (!(NWC_REL_SLACK * (omax + gmax) <= ctx->m.g.h)) return fail(ctx, NWC_ERR_BADARG, "nwc_cast: an origin lies more than 1e9 cells from the origin of the coordinates");
     a.up_o = !o_dev;
     a.up_d = !d_dev;
     a.up_sv = skip_vertex && !bq::on_device(skip_vertex);

@@ -49,7 +49,7 @@
 #pragma once
 #include "nw_intersections_core.h"
 
-#define NWC_RHO_SLACK 1e-9        // relative enlargement of rho_f (the intersection unit's NWX_SLACK)
+#define NWC_RHO_SLACK BQ_FACE_RHO_SLACK    // relative enlargement of rho_f (nw_bq_core.h: 1e-9)
 #define NWC_CELL_SLACK 1e-6       // of a cell, added to every box in cell units (the intersection unit's NWX_CELL_SLACK)
 #define NWC_REL_SLACK 1e-9        // of the largest coordinate, an absolute allowance for the rounding of points along a ray
 #define NWC_INFO_EXITS 1          // bit 0 of the info word: den > 0 at the nearest hit

@@ -1,9 +1,9 @@
 // The banded exact signed-distance volume of a triangle mesh on the device (MI355X, gfx950): include/nw_volume.h.
 //
-//   nwv_set_mesh    k_vx_face_setup   one thread per face: the float64 centroid and rho_f (nw_distance_core.h), a hair enlarged
-//                   k_vx_rho_reduce   rho_max and the sum of rho_f, one workgroup, a fixed order
-//                   (bq::bounds)      the centroids' box
-//   nwv_volume      (bq::size_grid, bq::build_grid)   the centroids binned at the cell size the band asks for, if the grid at hand has another
+//   nwv_set_mesh    (bq::FaceGrid::set_faces)   the mesh query units' shared intake (nw_bq.h): k_bq_face_setup, one thread per face, the
+//                                     float64 centroid and rho_f, a hair enlarged; k_bq_rho_reduce, rho_max and the sum of rho_f, one
+//                                     workgroup, a fixed order; bq::bounds, the centroids' box
+//   nwv_volume      (bq::FaceGrid::bin)   the centroids binned at the cell size the band asks for, if the grid at hand has another
 //                   k_vx_nodes        one lane per node: its own position from (lo, h, index), the capped ring walk of nw_volume_core.h,
 //                                     the band rule and, in band, the pseudonormal's sign; sd, face, and the block's counters
 //                   k_vx_seed         one workgroup over all faces for node (0, 0, 0): the (d2, face) lexicographic minimum, its
@@ -31,37 +31,6 @@
 #define NWV_PARTIALS 6            // per block: flag word, in-band nodes, rings near, centroids near, rings far, centroids far
 
 static_assert(sizeof(nwv_pt) == sizeof(bq::PtF64), "the walk reads the shared grid's sorted points in place");
-
-// ---- set-up ---------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(NWV_BLOCK) void k_vx_face_setup(const float *__restrict__ pos, const int *__restrict__ faces, int nf,
-                                                             double *__restrict__ cen, double *__restrict__ rho)
-{
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= nf) return;
-    const int a = faces[3 * (int64_t)f], b = faces[3 * (int64_t)f + 1], c = faces[3 * (int64_t)f + 2];
-    double m[3];
-    const double r = nwd_face_centroid(pos + 3 * (int64_t)a, pos + 3 * (int64_t)b, pos + 3 * (int64_t)c, m);
-    cen[3 * (int64_t)f] = m[0];
-    cen[3 * (int64_t)f + 1] = m[1];
-    cen[3 * (int64_t)f + 2] = m[2];
-    rho[f] = r * (1.0 + NWV_CORE_SLACK);
-}
-
-// out[0] = the largest rho, out[1] = their sum
-__global__ __launch_bounds__(NWV_BLOCK) void k_vx_rho_reduce(const double *__restrict__ rho, int nf, double *__restrict__ out)
-{
-    __shared__ double s_m[NWV_BLOCK / 64], s_s[NWV_BLOCK / 64];
-    double m = 0.0, s = 0.0;
-    for (int j = threadIdx.x; j < nf; j += NWV_BLOCK) { m = fmax(m, rho[j]); s += rho[j]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { m = fmax(m, __shfl_xor(m, o, 64)); s += __shfl_xor(s, o, 64); }
-    if ((threadIdx.x & 63) == 0) { s_m[threadIdx.x >> 6] = m; s_s[threadIdx.x >> 6] = s; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        out[0] = fmax(fmax(s_m[0], s_m[1]), fmax(s_m[2], s_m[3]));
-        out[1] = ((s_s[0] + s_s[1]) + s_s[2]) + s_s[3];
-    }
-}
 
 // ---- the nodes ------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NWV_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_vx_nodes(float lo0, float lo1, float lo2, float hv, int nx, int ny, int64_t nvox,
@@ -216,13 +185,9 @@ using bq::fail;
 using bq::nblk;
 
 struct nwv_ctx : bq::Ctx {
-    // the mesh of the last nwv_set_mesh
-    int nf = 0;                   // 0: the context holds no mesh
+    bq::FaceGrid m;               // the mesh of the last nwv_set_mesh and the grid at hand (m.nf == 0: the context holds no mesh)
     bool has_twin = false;
-    double rho_max = 0.0, rho_mean = 0.0;
-    bq::Grid<double> g{};         // lo, hi: the centroids' box; h, dims: the grid at hand
-    double h_start = 0.0;         // the cell size the grid at hand was sized from (0: none)
-    DevBuf mpos, mfaces, mtwin, cen, rho, red, mm, cell, ccount, cstart, sorted, scan_tmp;
+    DevBuf mtwin;
     // nwv_volume
     DevBuf sd, face, field, mask, partial, totals;
     int64_t n_field = 0;
@@ -232,51 +197,9 @@ namespace {
 
 #define NWV_HIP(call) BQ_HIP(call, NWV_ERR_NOMEM, NWV_ERR_HIP)
 
-// at most max(16 F, 65536) cells, up to 2^26; at most 1025 an axis; 400 widening steps (nwd_'s rule)
-const bq::GridRule NWV_GRID_RULE = {16, 1ll << 26, 1025, 400};
+const bq::FaceCodes NWV_FACE_CODES = {NWV_ERR_BADARG, NWV_ERR_NONFINITE, NWV_ERR_NOMEM, NWV_ERR_HIP};
 const int NWV_MAX_DIM = 1 << 20;
 const double NWV_MAX_CAP = 1099511627776.0;           // 2^40
-
-bool twin_ok(const int32_t *twin, int64_t nf)
-{
-    const int64_t nh = 3 * nf;
-    for (int64_t h = 0; h < nh; ++h) {
-        const int32_t t = twin[h];
-        if (t == -1) continue;
-        if (t < 0 || t >= nh || twin[t] != h) return false;
-    }
-    return true;
-}
-
-// the cell size a band starts from: twice the mean rho_f (a face or two per occupied cell of a surface) or half of d_cap + rho_max,
-// whichever is larger -- a far node then ends its walk after three or four rings, a few hundred cell ranges -- and at least a 1024th of
-// the widest axis; 1 for a mesh without extent
-double starting_cell(const nwv_ctx *ctx, double d_cap)
-{
-    double emax = 0.0;
-    for (int d = 0; d < 3; ++d) emax = std::max(emax, ctx->g.hi[d] - ctx->g.lo[d]);
-    if (!(emax > 0.0)) return 1.0;
-    double h = std::max(std::max(2.0 * ctx->rho_mean, (d_cap + ctx->rho_max) / 2.0), emax / 1024.0);
-    if (!(h > 0.0) || !std::isfinite(h)) h = emax;
-    return h;
-}
-
-// the grid for this band: the one at hand if it was sized from the same starting cell, else the centroids binned anew
-int ensure_grid(nwv_ctx *ctx, double d_cap)
-{
-    const double h0 = starting_cell(ctx, d_cap);
-    if (ctx->h_start == h0) return NWV_OK;
-    ctx->h_start = 0.0;
-    double ext[3];
-    for (int d = 0; d < 3; ++d) ext[d] = ctx->g.hi[d] - ctx->g.lo[d];
-    ctx->g.h = h0;
-    if (!bq::size_grid(NWV_GRID_RULE, ctx->nf, ext, &ctx->g.h, ctx->g.dims)) return fail(ctx, NWV_ERR_BADARG, "nwv_volume: no cell size keeps the grid within its cap");
-    int total = -1;
-    NWV_HIP(bq::build_grid<double>(ctx->stream, ctx->cen.as<double>(), ctx->nf, ctx->g, ctx->cell, ctx->ccount, ctx->scan_tmp, ctx->cstart, ctx->sorted, &total));
-    if (total != ctx->nf) return fail(ctx, NWV_ERR_HIP, "nwv_volume: the cell counts do not add up to the faces");
-    ctx->h_start = h0;
-    return NWV_OK;
-}
 
 }  // namespace
 
@@ -290,37 +213,16 @@ NWV_EXPORT const char *nwv_last_error(nwv_ctx *ctx) { return bq::last_error(ctx)
 
 NWV_EXPORT int nwv_set_mesh(nwv_ctx *ctx, const float *pos, int64_t n_vertices, const int32_t *faces, int64_t n_faces, const int32_t *twin)
 {
-    if (ctx) { ctx->nf = 0; ctx->h_start = 0.0; ctx->n_field = 0; }
-    if (!pos || !faces || n_vertices < 3 || n_faces < 1 || n_vertices > (1ll << 30) || n_faces > (1ll << 29)) return fail(ctx, NWV_ERR_BADARG, "nwv_set_mesh: a NULL array or a size out of range");
-    if (!bq::all_finite(pos, 3 * n_vertices)) return fail(ctx, NWV_ERR_NONFINITE, "nwv_set_mesh: a vertex position is not finite");
-    if (!bq::mesh_ok(pos, n_vertices, faces, n_faces)) return fail(ctx, NWV_ERR_BADARG, "nwv_set_mesh: a face index outside the vertices");
-    if (twin && !twin_ok(twin, n_faces)) return fail(ctx, NWV_ERR_BADARG, "nwv_set_mesh: the twin table is not -1 or an involution within [0, 3F)");
+    if (ctx) { ctx->m.nf = 0; ctx->n_field = 0; }
+    bq::FaceStatus s = bq::check_faces(pos, n_vertices, faces, n_faces);
+    if (!s.ok()) return bq::face_fail(ctx, "nwv_set_mesh", s, NWV_FACE_CODES);
+    if (twin && !bq::twin_ok(twin, n_faces)) return fail(ctx, NWV_ERR_BADARG, "nwv_set_mesh: the twin table is not -1 or an involution within [0, 3F)");
     if (!ctx) return NWV_ERR_BADARG;
     NWV_HIP(hipSetDevice(ctx->device));
-    const int nf = (int)n_faces;
-    NWV_HIP(bq::upload(ctx->stream, ctx->mpos, pos, 3 * n_vertices));
-    NWV_HIP(bq::upload(ctx->stream, ctx->mfaces, faces, 3 * n_faces));
     if (twin) NWV_HIP(bq::upload(ctx->stream, ctx->mtwin, twin, 3 * n_faces));
-    NWV_HIP(ctx->cen.ensure(sizeof(double) * 3 * (size_t)nf));
-    NWV_HIP(ctx->rho.ensure(sizeof(double) * (size_t)nf));
-    NWV_HIP(ctx->red.ensure(sizeof(double) * 2));
-    hipLaunchKernelGGL(k_vx_face_setup, dim3(nblk(nf)), dim3(NWV_BLOCK), 0, ctx->stream, ctx->mpos.as<float>(), ctx->mfaces.as<int>(), nf,
-                       ctx->cen.as<double>(), ctx->rho.as<double>());
-    hipLaunchKernelGGL(k_vx_rho_reduce, dim3(1), dim3(NWV_BLOCK), 0, ctx->stream, ctx->rho.as<double>(), nf, ctx->red.as<double>());
-    NWV_HIP(hipGetLastError());
-    double red[2] = {0.0, 0.0};
-    NWV_HIP(hipMemcpyAsync(red, ctx->red.p, sizeof(red), hipMemcpyDeviceToHost, ctx->stream));
-    NWV_HIP(hipStreamSynchronize(ctx->stream));                   // (red is a stack array, and the uploads' sources are the caller's)
-    bool finite[2];
-    NWV_HIP(bq::bounds<double>(ctx->stream, ctx->mm, ctx->cen.as<double>(), nf, nullptr, 0, &ctx->g, finite));
-    if (!finite[0] || !std::isfinite(red[0]) || !std::isfinite(red[1])) return fail(ctx, NWV_ERR_NONFINITE, "nwv_set_mesh: a face's centroid or radius is not a finite double");
-    double emax = 0.0;
-    for (int d = 0; d < 3; ++d) emax = std::max(emax, ctx->g.hi[d] - ctx->g.lo[d]);
-    if (!std::isfinite(emax)) return fail(ctx, NWV_ERR_BADARG, "nwv_set_mesh: the mesh's extent is not a finite double");
-    ctx->rho_max = red[0];
-    ctx->rho_mean = red[1] / (double)nf;
+    s = ctx->m.set_faces(ctx->stream, pos, n_vertices, faces, n_faces);
+    if (!s.ok()) return bq::face_fail(ctx, "nwv_set_mesh", s, NWV_FACE_CODES);
     ctx->has_twin = twin != nullptr;
-    ctx->nf = nf;
     return NWV_OK;
 }
 
@@ -337,12 +239,14 @@ NWV_EXPORT int nwv_volume(nwv_ctx *ctx, const float *lo, float h, const int32_t 
     }
     if (nvox > (1ll << 30)) return fail(ctx, NWV_ERR_BADARG, "nwv_volume: more than 2^30 nodes");
     if (!ctx) return NWV_ERR_BADARG;
-    if (ctx->nf < 1) return fail(ctx, NWV_ERR_NOMESH, "nwv_volume: the context holds no mesh");
+    if (ctx->m.nf < 1) return fail(ctx, NWV_ERR_NOMESH, "nwv_volume: the context holds no mesh");
     const bool is_signed = (flags & NWV_SIGNED) != 0;
     if (is_signed && !ctx->has_twin) return fail(ctx, NWV_ERR_BADARG, "nwv_volume: NWV_SIGNED needs the twin table that nwv_set_mesh was not given");
     NWV_HIP(hipSetDevice(ctx->device));
-    const int r = ensure_grid(ctx, d_cap);
-    if (r != NWV_OK) return r;
+    bq::FaceGrid &m = ctx->m;
+    // the grid for this band, from the cell size bq::band_cell and bq::face_cell give
+    const bq::FaceStatus s = m.bin(ctx->stream, bq::face_cell(bq::band_cell(m.rho_mean, m.rho_max, d_cap), m.emax()));
+    if (!s.ok()) return bq::face_fail(ctx, "nwv_volume", s, NWV_FACE_CODES);
     const int nb = nblk(nvox, NWV_BLOCK);
     const int nx = dims[0], ny = dims[1], nz = dims[2];
     NWV_HIP(ctx->sd.ensure(sizeof(double) * (size_t)nvox));
@@ -352,18 +256,18 @@ NWV_EXPORT int nwv_volume(nwv_ctx *ctx, const float *lo, float h, const int32_t 
     NWV_HIP(ctx->partial.ensure(sizeof(long long) * NWV_PARTIALS * (size_t)nb));
     NWV_HIP(ctx->totals.ensure(sizeof(long long) * (NWV_PARTIALS + 1)));
     nwv_grid g;
-    for (int d = 0; d < 3; ++d) { g.lo[d] = ctx->g.lo[d]; g.hi[d] = ctx->g.hi[d]; g.dims[d] = ctx->g.dims[d]; }
-    g.h = ctx->g.h;
+    for (int d = 0; d < 3; ++d) { g.lo[d] = m.g.lo[d]; g.hi[d] = m.g.hi[d]; g.dims[d] = m.g.dims[d]; }
+    g.h = m.g.h;
     const int *twin = is_signed ? ctx->mtwin.as<int>() : nullptr;
     double *sd = ctx->sd.as<double>();
     int *face = ctx->face.as<int>();
     long long *totals = ctx->totals.as<long long>();
-    hipLaunchKernelGGL(k_vx_nodes, dim3(nb), dim3(NWV_BLOCK), 0, ctx->stream, lo[0], lo[1], lo[2], h, nx, ny, nvox, ctx->mpos.as<float>(), ctx->mfaces.as<int>(),
-                       twin, ctx->nf, ctx->sorted.as<nwv_pt>(), ctx->cstart.as<int>(), ctx->rho.as<double>(), ctx->rho_max, g, d_cap, sd, face,
+    hipLaunchKernelGGL(k_vx_nodes, dim3(nb), dim3(NWV_BLOCK), 0, ctx->stream, lo[0], lo[1], lo[2], h, nx, ny, nvox, m.mpos.as<float>(), m.mfaces.as<int>(),
+                       twin, m.nf, m.sorted.as<nwv_pt>(), m.cstart.as<int>(), m.rho.as<double>(), m.rho_max, g, d_cap, sd, face,
                        ctx->partial.as<long long>());
     if (is_signed) {
-        hipLaunchKernelGGL(k_vx_seed, dim3(1), dim3(NWV_BLOCK), 0, ctx->stream, lo[0], lo[1], lo[2], h, ctx->mpos.as<float>(), ctx->mfaces.as<int>(), twin,
-                           ctx->nf, d_cap, sd, face, totals + NWV_PARTIALS);
+        hipLaunchKernelGGL(k_vx_seed, dim3(1), dim3(NWV_BLOCK), 0, ctx->stream, lo[0], lo[1], lo[2], h, m.mpos.as<float>(), m.mfaces.as<int>(), twin,
+                           m.nf, d_cap, sd, face, totals + NWV_PARTIALS);
         for (int stage = 0; stage < 3; ++stage) {
             int64_t n_lines, pitch, n, stride;
             nwv_sweep_stage(stage, nx, ny, nz, &n_lines, &pitch, &n, &stride);
@@ -381,7 +285,7 @@ NWV_EXPORT int nwv_volume(nwv_ctx *ctx, const float *lo, float h, const int32_t 
     NWV_HIP(hipStreamSynchronize(ctx->stream));
     if (info_out) {
         for (int c = 0; c < NWV_PARTIALS; ++c) info_out[c] = tot[c];
-        info_out[NWV_INFO_CELLS] = ctx->g.cells();
+        info_out[NWV_INFO_CELLS] = m.g.cells();
         info_out[NWV_INFO_SEED_FACE] = tot[NWV_PARTIALS];
     }
     ctx->n_field = nvox;

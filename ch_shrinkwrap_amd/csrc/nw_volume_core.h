@@ -32,7 +32,7 @@
 #include "nw_distance_core.h"
 
 #define NWV_FIELD_SHIFT 20
-#define NWV_CORE_SLACK 1e-9       // relative slack of every bound: far above the rounding of a float64 distance, far below what matters
+#define NWV_CORE_SLACK BQ_FACE_RHO_SLACK      // (nw_bq_core.h: 1e-9) relative slack of every bound: far above the rounding of a float64 distance, far below what matters
 
 // the centroid grid as the walk reads it (the layout of the query units' shared grid in double) and a sorted centroid with its face id
 struct nwv_grid {

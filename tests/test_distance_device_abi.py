@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = ['k_md_face_setup', 'k_md_rho_reduce', 'k_md_query', 'k_md_sum_final']
+KERNELS = ['k_md_query', 'k_md_sum_final']              # (the set-up kernels are the face grid's: k_bq_face_setup, k_bq_rho_reduce of nw_bq.o)
 
 
 def _declared():

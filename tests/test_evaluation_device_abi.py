@@ -13,6 +13,7 @@ KERNELS = ['k_ev_face_setup', 'k_ev_node_test', 'k_ev_emit', 'k_ev_nearest', 'k_
 GRID_KERNELS = {'k_bq_bbox_f64': (48, 0), 'k_bq_cell_count_f64': (48, 0), 'k_bq_scatter_f64': (16, 0),
                 'k_bq_bbox_f32': (32, 0), 'k_bq_cell_count_f32': (32, 0), 'k_bq_scatter_f32': (32, 0)}
 SCAN_KERNELS = ['k_bq_scan_tiles', 'k_bq_scan_bsums', 'k_bq_scan_final']
+FACE_KERNELS = ['k_bq_face_setup', 'k_bq_rho_reduce']           # the mesh query units' face grid
 
 
 def _declared():
@@ -39,7 +40,7 @@ def test_evaluation_kernels_are_budgeted_and_within_budget():
     assert build.OBJ_EVALUATION in build.BUDGETED_OBJECTS and build.OBJ_BQ in build.BUDGETED_OBJECTS
     in_object = build.kernel_resources(build.OBJ_EVALUATION)
     assert sorted(in_object) == sorted(KERNELS)                  # every kernel of the unit has a row, and no row is stale
-    assert sorted(build.kernel_resources(build.OBJ_BQ)) == sorted(list(GRID_KERNELS) + SCAN_KERNELS)
+    assert sorted(build.kernel_resources(build.OBJ_BQ)) == sorted(list(GRID_KERNELS) + SCAN_KERNELS + FACE_KERNELS)
     assert not [k for k in build.KERNEL_BUDGETS if k.startswith('k_ev_') and k not in KERNELS]
     for k, budget in GRID_KERNELS.items():
         assert build.KERNEL_BUDGETS[k] == budget, k

@@ -288,6 +288,6 @@ def test_surface_density_and_the_recipe_on_a_sphere_with_one_hemisphere_four_tim
 def test_the_kernel_budgets_hold_with_the_new_rows():
     """(reads the object files the build leaves in csrc/, as tests/test_mapping_device_abi.py does without a GPU)"""
     res = build.check_kernel_budgets()
-    for k in ('k_lm_face_setup', 'k_lm_rho_reduce', 'k_lm_map', 'k_lm_totals'):
+    for k in ('k_lm_face_setup', 'k_bq_face_setup', 'k_bq_rho_reduce', 'k_lm_map', 'k_lm_totals'):
         assert k in build.KERNEL_BUDGETS and res[k]['scratch'] == 0
     assert build.KERNEL_BUDGETS['k_lm_map'][0] == build.KERNEL_BUDGETS['k_vx_nodes'][0] == 128

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = ['k_mx_face_setup', 'k_mx_rho_reduce', 'k_mx_count', 'k_mx_emit', 'k_mx_stats', 'k_mx_totals']
+KERNELS = ['k_mx_count', 'k_mx_emit', 'k_mx_stats', 'k_mx_totals']
 
 
 def _declared():
@@ -62,7 +62,10 @@ def test_the_distance_unit_is_left_alone():
     build.build_hip_library()
     assert not [k for k in build.kernel_resources(build.OBJ_DISTANCE) if k.startswith('k_mx_')]
     core = open(os.path.join(ROOT, 'ch_shrinkwrap_amd', 'csrc', 'nw_intersections_core.h')).read()
-    assert re.findall(r'#include\s+[<"]([^>"]+)[>"]', core) == ['cmath', 'cstdint']                      # HIP-free
+    # HIP-free: the standard headers and the query units' shared HIP-free core (the one definition of a face's centroid and radius)
+    assert re.findall(r'#include\s+[<"]([^>"]+)[>"]', core) == ['cmath', 'cstdint', 'nw_bq_core.h']
+    shared = open(os.path.join(ROOT, 'ch_shrinkwrap_amd', 'csrc', 'nw_bq_core.h')).read()
+    assert re.findall(r'#include\s+[<"]([^>"]+)[>"]', shared) == ['cstdint', 'cmath', 'algorithm']
 
 
 def test_arguments_are_refused_before_any_hip_call():

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = ['k_lm_face_setup', 'k_lm_rho_reduce', 'k_lm_map', 'k_lm_totals']
+KERNELS = ['k_lm_face_setup', 'k_lm_map', 'k_lm_totals']
 
 
 def _declared():

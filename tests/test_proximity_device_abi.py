@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = ['k_mm_face_setup', 'k_mm_rho_reduce', 'k_mm_query', 'k_mm_finish', 'k_mm_totals']
+KERNELS = ['k_mm_query', 'k_mm_finish', 'k_mm_totals']
 
 
 def _declared():
@@ -60,8 +60,8 @@ def test_unit_is_built_without_contraction_and_budgeted():
 
 
 def test_the_unit_is_new_and_the_core_reuses_the_two_cores():
-    """the point-triangle distance and the centroid are nw_distance_core.h's, the segment-face test nw_intersections_core.h's: included
-    and not copied; the kernels are in an object of their own, and no other unit has gained or lost one"""
+    """the point-triangle distance is nw_distance_core.h's, the segment-face test nw_intersections_core.h's, the centroid the shared
+    face grid's (nw_bq_core.h, which nwd_face_centroid forwards to): included and not copied; the kernels are in an object of their own, and no other unit has gained or lost one"""
     from ch_shrinkwrap_amd import build
     build.build_hip_library()
     core = open(os.path.join(ROOT, 'ch_shrinkwrap_amd', 'csrc', 'nw_proximity_core.h')).read()
@@ -71,7 +71,13 @@ def test_the_unit_is_new_and_the_core_reuses_the_two_cores():
     for name in ('nwd_point_triangle', 'nwx_seg_tri', 'nwx_normal'):
         assert name + '(' in core
     src = open(os.path.join(ROOT, 'ch_shrinkwrap_amd', 'csrc', 'nw_proximity.hip')).read()
-    assert 'nwd_face_centroid(' in src
+    # the centroid and radius of A's and of B's faces come from the shared face grid's one kernel (nw_bq.hip), for both meshes the same
+    code = re.sub(r'//.*', '', src)
+    assert 'bq::face_setup(' in code and 'set_faces(' in code and '__global__' in code and 'face_setup(const' not in code
+    bq_src = re.sub(r'//.*', '', open(os.path.join(ROOT, 'ch_shrinkwrap_amd', 'csrc', 'nw_bq.hip')).read())
+    assert 'bq::face_centroid(' in bq_src
+    dist_core = open(os.path.join(ROOT, 'ch_shrinkwrap_amd', 'csrc', 'nw_distance_core.h')).read()
+    assert re.search(r'nwd_face_centroid\([^)]*\)\s*\{\s*return bq::face_centroid\(', dist_core)
     assert '"nw_proximity_core.h"' in src and '"nw_bq.h"' in src and 'atomic' not in re.sub(r'//.*', '', src)
     for obj in (build.OBJ_DISTANCE, build.OBJ_INTERSECTIONS, build.OBJ_RAYS, build.OBJ_VOLUME, build.OBJ_BQ):
         assert not [k for k in build.kernel_resources(obj) if k.startswith('k_mm_')]

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = ['k_vx_face_setup', 'k_vx_rho_reduce', 'k_vx_nodes', 'k_vx_seed', 'k_vx_sweep', 'k_vx_finish', 'k_vx_totals']
+KERNELS = ['k_vx_nodes', 'k_vx_seed', 'k_vx_sweep', 'k_vx_finish', 'k_vx_totals']
 
 
 def _declared():

@@ -4,7 +4,7 @@ usage: python tools/proximity_profile.py [scale] [iterations] [mesh.npz | -] [sw
        the scene: config C3's mesh after a short fit (A) against a copy of itself shifted by SHIFT so that the two overlap in part (B);
        bands 30 nm and inf.  mesh.npz: where the fitted mesh is kept between runs (made if it is not there; - for none)
        sweep: after the report, the query's time and counters at explicit cell sizes (SWEEP), the measurement the unit's own choice
-       of cell size (starting_cell in csrc/nw_proximity.hip) rests on
+       of cell size (nwm_band_cell in csrc/nw_proximity_core.h) rests on
        rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/proximity_profile.py 1.0 10 mesh.npz
                                                                        (device time per kernel, a run of its own)"""
 import os, sys, time
