@@ -47,6 +47,7 @@ OBJ_CLUSTERING = _csrc('nw_clustering.o')
 OBJ_PAIRS = _csrc('nw_pairs.o')
 OBJ_GEODESIC = _csrc('nw_geodesic.o')
 OBJ_SKELETON = _csrc('nw_skeleton.o')
+OBJ_STRUCTURE = _csrc('nw_structure.o')
 # the translation units of libnanowrap_hip.so: (source, object, what else it is rebuilt for, flags).  The objects are linked in this order.
 UNITS = [
     # the per-iteration kernels and the C-ABI; every header of csrc/ but nw_bq.h and nw_bq_core.h is included by it (directly or through
@@ -115,6 +116,12 @@ UNITS = [
     # arcs (nw_skeleton_core.h: the band rule, the piece index, the crossing point, the quantisation and the proof that no sum overflows,
     # which the tests also compile for the CPU; it includes nothing of the project's)
     (_csrc('nw_skeleton.hip'), OBJ_SKELETON, [_include('nw_skeleton.h'), _csrc('nw_skeleton_core.h')] + _BQ_H, _QUERY),
+    # the local shape of the cloud: the integer moments of every neighbourhood of radius r, and their covariance's eigenvalues and
+    # eigenvectors (nw_structure_core.h: the neighbourhood, the quantisation, the moments with the proof that no sum overflows, the
+    # covariance and the Jacobi iteration in a written order, and the walk over a clamped box of cells, which the tests also compile for
+    # the CPU; it includes nw_neighbours_core.h for the squared distance and the cell slack)
+    (_csrc('nw_structure.hip'), OBJ_STRUCTURE, [_include('nw_structure.h'), _csrc('nw_structure_core.h'), _csrc('nw_neighbours_core.h')] + _BQ_H,
+     _QUERY),
 ]
 DEPS = sorted(set(d for src, _, extra, _ in UNITS for d in [src] + extra))
 
@@ -289,6 +296,12 @@ KERNEL_BUDGETS = {
     'k_sk_sums':                      (64, 0),             # three corners in float64, two crossing points, twelve 64-bit terms
     'k_sk_arcs':                      (16, 0),
     'k_sk_vertex':                    (16, 0),
+    # the local shape of the cloud (csrc/nw_structure.o): one lane per query, its ten 64-bit sums in registers, no atomics on the results;
+    # zero scratch
+    'k_st_order':                     (8, 0),
+    'k_st_moments':                   (64, 64),            # the query in float64, the walk's ranges, ten 64-bit sums (62 VGPRs): 8 waves per SIMD; LDS = the two waves' four counters
+    'k_st_eigen':                     (64, 0),             # six elements of C, nine of V and a rotation in flight, all float64 (60 VGPRs): 8 waves per SIMD
+    'k_st_totals':                    (24, 2048),          # LDS = one 64-bit sum per thread
     # what the eleven units above share (csrc/nw_bq.o), and nw_mapping.o: the exclusive scan, and the point grid of hole punching (f32) and of the metric (f64)
     'k_bq_scan_tiles':                (32, 1024),
     'k_bq_scan_bsums':                (32, 1024),
@@ -303,7 +316,7 @@ KERNEL_BUDGETS = {
     'k_bq_face_setup':                (56, 0),
     'k_bq_rho_reduce':                (24, 64),            # LDS = the four waves' maxima and sums
 }
-BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_DISTANCE, OBJ_NEIGHBOURS, OBJ_INTERSECTIONS, OBJ_RAYS, OBJ_VOLUME, OBJ_PROXIMITY, OBJ_MAPPING, OBJ_CLUSTERING, OBJ_PAIRS, OBJ_GEODESIC, OBJ_SKELETON, OBJ_BQ]
+BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_DISTANCE, OBJ_NEIGHBOURS, OBJ_INTERSECTIONS, OBJ_RAYS, OBJ_VOLUME, OBJ_PROXIMITY, OBJ_MAPPING, OBJ_CLUSTERING, OBJ_PAIRS, OBJ_GEODESIC, OBJ_SKELETON, OBJ_STRUCTURE, OBJ_BQ]
 
 
 def kernel_resources(obj=None):
