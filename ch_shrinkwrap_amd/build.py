@@ -48,6 +48,7 @@ OBJ_PAIRS = _csrc('nw_pairs.o')
 OBJ_GEODESIC = _csrc('nw_geodesic.o')
 OBJ_SKELETON = _csrc('nw_skeleton.o')
 OBJ_STRUCTURE = _csrc('nw_structure.o')
+OBJ_POISSON = _csrc('nw_poisson.o')
 # the translation units of libnanowrap_hip.so: (source, object, what else it is rebuilt for, flags).  The objects are linked in this order.
 UNITS = [
     # the per-iteration kernels and the C-ABI; every header of csrc/ but nw_bq.h and nw_bq_core.h is included by it (directly or through
@@ -122,8 +123,13 @@ UNITS = [
     # the CPU; it includes nw_neighbours_core.h for the squared distance and the cell slack)
     (_csrc('nw_structure.hip'), OBJ_STRUCTURE, [_include('nw_structure.h'), _csrc('nw_structure_core.h'), _csrc('nw_neighbours_core.h')] + _BQ_H,
      _QUERY),
+    # the screened Poisson grid solver, the comparator of the evaluation: integer splats of an oriented cloud, the system of a level, red-black
+    # sweeps, prolongation, the uint64 field (nw_poisson_core.h: a sample's weights, the depth rule, a node's row, one update, the residual,
+    # the prolongation and the quantisation with the proofs that no sum overflows, which the tests also compile for the CPU; it includes
+    # nothing of the project's)
+    (_csrc('nw_poisson.hip'), OBJ_POISSON, [_include('nw_poisson.h'), _csrc('nw_poisson_core.h')] + _BQ_H, _QUERY),
 ]
-DEPS = sorted(set(d for src, _, extra, _ in UNITS for d in [src] + extra))
+DEPS =sorted(set(d for src, _, extra, _ in UNITS for d in [src] + extra))
 
 
 def needs_build():
@@ -302,6 +308,21 @@ KERNEL_BUDGETS = {
     'k_st_moments':                   (64, 64),            # the query in float64, the walk's ranges, ten 64-bit sums (62 VGPRs): 8 waves per SIMD; LDS = the two waves' four counters
     'k_st_eigen':                     (64, 0),             # six elements of C, nine of V and a rotation in flight, all float64 (60 VGPRs): 8 waves per SIMD
     'k_st_totals':                    (24, 2048),          # LDS = one 64-bit sum per thread
+    # the screened Poisson grid solver (csrc/nw_poisson.o): one lane per sample, per node or per pair of x-neighbours; 64-bit integer atomics
+    # whose results are not read, no float atomics; zero scratch (a node's three coordinates are walked by an unrolled loop).  All of them
+    # reach 8 waves per SIMD; LDS = the four waves' partial sums or maxima
+    'k_sp_prepare':                   (24, 32),
+    'k_sp_mark':                      (32, 0),
+    'k_sp_count':                     (16, 32),
+    'k_sp_splat':                     (40, 0),             # three axes' two nodes and weights, the normal, one product in flight
+    'k_sp_splat_lds':                 (56, 16 * 1024),     # the same over a copy of levels 2 and 3 in LDS (4 planes of 512 nodes) and a loop over the samples
+    'k_sp_splat_lds4':                (56, 128 * 1024),    # the same for level 4 (4 planes of 4096 nodes): one workgroup a CU
+    'k_sp_system':                    (24, 0),
+    'k_sp_prolong':                   (32, 0),             # eight coarse values
+    'k_sp_relax':                     (16, 0),             # the stencil of one node: bound by memory, not by registers
+    'k_sp_residual':                  (16, 32),
+    'k_sp_absmax':                    (8, 32),
+    'k_sp_field':                     (24, 32),
     # what the eleven units above share (csrc/nw_bq.o), and nw_mapping.o: the exclusive scan, and the point grid of hole punching (f32) and of the metric (f64)
     'k_bq_scan_tiles':                (32, 1024),
     'k_bq_scan_bsums':                (32, 1024),
@@ -316,7 +337,7 @@ KERNEL_BUDGETS = {
     'k_bq_face_setup':                (56, 0),
     'k_bq_rho_reduce':                (24, 64),            # LDS = the four waves' maxima and sums
 }
-BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_DISTANCE, OBJ_NEIGHBOURS, OBJ_INTERSECTIONS, OBJ_RAYS, OBJ_VOLUME, OBJ_PROXIMITY, OBJ_MAPPING, OBJ_CLUSTERING, OBJ_PAIRS, OBJ_GEODESIC, OBJ_SKELETON, OBJ_STRUCTURE, OBJ_BQ]
+BUDGETED_OBJECTS = [OBJ_MAIN, OBJ_HOLEPUNCH, OBJ_SURGERY, OBJ_ISOSURFACE, OBJ_EVALUATION, OBJ_SIMULATION, OBJ_DISTANCE, OBJ_NEIGHBOURS, OBJ_INTERSECTIONS, OBJ_RAYS, OBJ_VOLUME, OBJ_PROXIMITY, OBJ_MAPPING, OBJ_CLUSTERING, OBJ_PAIRS, OBJ_GEODESIC, OBJ_SKELETON, OBJ_STRUCTURE, OBJ_POISSON, OBJ_BQ]
 
 
 def kernel_resources(obj=None):
