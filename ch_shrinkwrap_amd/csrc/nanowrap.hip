@@ -161,6 +161,8 @@ struct nw_ctx {
     DevBuf<NwItem> items;             // work list of the NN query: runs of <= 64 Morton-consecutive localizations
     DevBuf<unsigned> item_cost;       // measured duration of every item in the last query (until the list has been ordered by it)
     bool handoff_off = false;         // NW_ERR_HANDOFF was raised once: the attraction step stays a launch of its own
+    int armed_status = 0;             // nw_debug(what = 8): the status the next block's begin writes into the device state (0: none)
+    int armed_word = 0;               // ... and the host word that copy reads (it must outlive the asynchronous copy)
     DevBuf<int> query_serial;         // number of grid builds so far (k_face_centroids): the value a finished item's word takes
     DevBuf<int> item_done;            // per work item: the number of the last iteration whose query has left it (the attraction workgroups of the same launch poll it)
     bool items_by_cost = false;       // the list has been ordered longest-first (once per work list)
@@ -1534,7 +1536,11 @@ NW_EXPORT int nw_optimize_layout(nw_ctx *ctx)
     // (a fraction of a millisecond) then does not fall into the caller's next block either.  A different next block just captures again.
     if (ctx->searched && ctx->search_iters > 0 && ctx->face_warm) {
         const float lam = ctx->lam0;
-        NW_TRY(nw_search_begin(ctx, &lam, 1, ctx->search_iters, ctx->search_flags));
+        const int armed = ctx->armed_status;                 // (nw_debug(what = 8) is for the next block that runs, not for this recording)
+        ctx->armed_status = 0;
+        const int rb = nw_search_begin(ctx, &lam, 1, ctx->search_iters, ctx->search_flags);
+        ctx->armed_status = armed;
+        NW_TRY(rb);
         ctx->direct_out = ctx->last_direct_out;             // (part of what the graph bakes in: where the last update writes the result)
         (void)block_graph(ctx, ctx->search_iters, ctx->profiling == 4);      // (level 4: everything before the block's last iteration)
         ctx->direct_out = false;
@@ -1578,6 +1584,13 @@ NW_EXPORT int nw_search_begin(nw_ctx *ctx, const float *lams, int n_lams, int nu
     ctx->search_done = 0;
     NW_HIP(ctx->logs.ensure((size_t)std::max(num_iters, 1)));
     hipLaunchKernelGGL(k_set_iter_base, dim3(1), dim3(1), 0, ctx->stream, ctx->state.p, ctx->global_iter);
+    if (ctx->armed_status != 0) {
+        // nw_debug(what = 8): the block starts with this status in the device state, as if its first attraction step had raised it.  A copy
+        // of one word on the stream, in front of the block's first launch and of any recorded range (not in block_graph_key()); one block only
+        ctx->armed_word = ctx->armed_status;
+        ctx->armed_status = 0;
+        NW_HIP(hipMemcpyAsync((char *)ctx->state.p + offsetof(NwDevState, status), &ctx->armed_word, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    }
     if (ctx->profiling) { ctx->ev_used = 0; g_marks.spans.clear(); for (int k = 0; k < ST_COUNT; ++k) { ctx->stage_ms[k] = 0; ctx->stage_launches[k] = 0; } }
     ctx->in_search = true;
     ctx->begin_ops_pending = true;         // the stream operations of the block's start are issued with its first iteration (or captured)
@@ -2737,7 +2750,8 @@ static int debug_nn_stats(nw_ctx *ctx, int64_t *out)
 // developer aids behind one entry point (not part of the drop-in surface): what = 0: counters of the NN query since the last call
 // (a = int64[NWS_COUNT + 1]; the first call switches the counting on); what = 1: the query's work list (a = int32 {p0, n}[cap], b =
 // uint32 cost[cap] (2 cap with NW_ITEM_TIMES), *n = items in the list); what = 7: which path the blocks of nw_search took so far
-// (a = int64[3]: {blocks recorded as a hipGraph, blocks replayed from one, blocks launched directly})
+// (a = int64[3]: {blocks recorded as a hipGraph, blocks replayed from one, blocks launched directly}); what = 8: the next block starts with
+// the status `cap` in its device state (a = int64[2]: {the code armed before, handoff_off})
 NW_EXPORT int nw_debug(nw_ctx *ctx, int what, void *a, void *b, int cap, int *n)
 {
     if (what == 0) return debug_nn_stats(ctx, (int64_t *)a);
@@ -2768,6 +2782,16 @@ NW_EXPORT int nw_debug(nw_ctx *ctx, int what, void *a, void *b, int cap, int *n)
     if (what == 7 && ctx && a) {
         int64_t *o = (int64_t *)a;
         o[0] = ctx->n_blocks_captured; o[1] = ctx->n_blocks_replayed; o[2] = ctx->n_blocks_direct;
+        return NW_OK;
+    }
+    if (what == 8 && ctx) {
+        // cap = the status the next block starts with in its device state (nw_search_begin writes it in front of the block's first launch, then
+        // disarms); 0 disarms.  a (optional) = int64[2]: {the code armed before this call, handoff_off}, also when the call is refused
+        if (a) { ((int64_t *)a)[0] = ctx->armed_status; ((int64_t *)a)[1] = ctx->handoff_off ? 1 : 0; }
+        if (ctx->in_search) return fail(ctx, NW_ERR_BADARG, "nw_debug(8) inside a search");
+        if (cap != 0 && cap != NW_ERR_NAN && cap != NW_ERR_SINGULAR && cap != NW_ERR_INTERNAL && cap != NW_ERR_HANDOFF)
+            return fail(ctx, NW_ERR_BADARG, "nw_debug(8): the code must be 0 or one of NW_ERR_NAN, NW_ERR_SINGULAR, NW_ERR_INTERNAL, NW_ERR_HANDOFF");
+        ctx->armed_status = cap;
         return NW_OK;
     }
     if ((what == 5 || what == 6) && ctx && a && b && n) {

@@ -71,6 +71,8 @@ def _as_f32(a):
 class ShrinkwrapMeshConjGrad(object):
     """MI355X-native counterpart of ch_shrinkwrap.mesh_conj_grad.ShrinkwrapMeshConjGrad (mesh_conj_grad.py:20)."""
 
+    handoff_retries = 1          # how often search() runs a block again after NW_ERR_HANDOFF (tests set 0 to see the raw code)
+
     def __init__(self, mesh, points, sigma=None, search_k=200, search_rad=100, shield_sigma=None, use_octree=False,
                  device=0, native=None, stream=None, reuse_device_mesh=False, device_tables=False):
         # TikhonovConjugateGradient.__init__ (conj_grad.py:35-43)
@@ -256,8 +258,9 @@ class ShrinkwrapMeshConjGrad(object):
         self._cache = {}
         if not to_host:
             code = self._L.nw_search(self._h, nw.ptr(lams_a), lams_a.size, num_iters, flags, None, logs, ctypes.byref(lc))
+            code, logs, done = self._rerun_after_handoff(code, logs, lc, lams_a, num_iters, flags, None)
             self._native.check(code)
-            self._consume_logs(logs, lc.value)
+            self._consume_logs(logs, lc.value, done)
             self._accumulate_stage_ms()
             return None
         # write-back (mesh_conj_grad.py:288-290) inside the call: the library copies the positions out in slices (the (M,3) result and
@@ -270,12 +273,14 @@ class ShrinkwrapMeshConjGrad(object):
         direct = posv.dtype == np.float32 and posv.strides[1] == 4 and posv.strides[0] >= 12
         deferred = records is not None and direct and _ROWS_ASYNC and num_iters > 0
         self._native.check(self._L.nw_set_write_back(self._h, ctypes.c_void_p(posv.ctypes.data) if direct else None, posv.strides[0] if direct else 0))
-        code = self._L.nw_search(self._h, nw.ptr(lams_a), lams_a.size, num_iters, flags | (nw.NW_FLAG_ROWS_ASYNC if deferred else 0), nw.ptr(out), logs, ctypes.byref(lc))
+        flags |= nw.NW_FLAG_ROWS_ASYNC if deferred else 0
+        code = self._L.nw_search(self._h, nw.ptr(lams_a), lams_a.size, num_iters, flags, nw.ptr(out), logs, ctypes.byref(lc))
         if deferred:
             self.mesh.__dict__['_rows_pending'] = self._flush_rows      # (before anything can raise: the rows may be in flight)
+        code, logs, done = self._rerun_after_handoff(code, logs, lc, lams_a, num_iters, flags, nw.ptr(out))
         self._native.check(self._L.nw_set_write_back(self._h, None, 0))
         self._native.check(code)
-        self._consume_logs(logs, lc.value)
+        self._consume_logs(logs, lc.value, done)
         self._accumulate_stage_ms()
         if not direct:                          # exotic vertex layout: let NumPy do the strided copy
             np.copyto(posv, out, where=self._mesh_vertex_mask[:, None])
@@ -301,8 +306,24 @@ class ShrinkwrapMeshConjGrad(object):
         """Device stream drained and host-side copies finished (nw_synchronize)."""
         self._flush_rows()
 
-    def _consume_logs(self, logs, executed):
-        self.loopcount = executed
+    def _rerun_after_handoff(self, code, logs, lc, lams_a, num_iters, flags, out):
+        """NW_ERR_HANDOFF says "run the block again" (include/nanowrap.h): the attraction step inside the query launch gave up on its work
+        item, nothing of that iteration was applied, and the context now runs the two steps as launches of their own.  The iterations
+        that did run keep their logs; the rest of the block is asked for again, `handoff_retries` times at the most.  Returns the status
+        and the logs of the last call (lc holds its count); every other status passes through untouched."""
+        done, retries = 0, int(self.handoff_retries)
+        while code == nw.NW_ERR_HANDOFF and retries > 0 and num_iters - done - lc.value > 0:
+            retries -= 1
+            self._consume_logs(logs, lc.value, done)
+            done += lc.value
+            logs = (nw.IterLog * (num_iters - done))()
+            lc.value = 0
+            code = self._L.nw_search(self._h, nw.ptr(lams_a), lams_a.size, num_iters - done, flags, out, logs, ctypes.byref(lc))
+        return code, logs, done
+
+    def _consume_logs(self, logs, executed, before=0):
+        """`before`: iterations of this block that an earlier nw_search of the same search() ran (their logs are consumed already)"""
+        self.loopcount = before + executed
         for i in range(executed):
             L = logs[i]
             self.tests.append(np.float32(L.test))

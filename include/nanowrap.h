@@ -359,7 +359,15 @@ int nw_accumulator_quantum(nw_ctx *ctx, double *q);
  *   *n = localizations kept (0: nothing).
  * what = 7: a = int64 out[3]: which path the blocks of nw_search took so far -- {blocks recorded as a hipGraph (nw_optimize_layout's
  *   pre-recording included), blocks replayed from a recorded graph (at profiling level 4: the head of the block), blocks whose launches
- *   all came from the host}.  A recording that fails silently shows as direct blocks, a key that changes as one more recording. */
+ *   all came from the host}.  A recording that fails silently shows as direct blocks, a key that changes as one more recording.
+ * what = 8: cap = one of NW_ERR_NAN, NW_ERR_SINGULAR, NW_ERR_INTERNAL, NW_ERR_HANDOFF arms the ctx: the next block's begin writes that code
+ *   into the status word of the device state (a 4-byte copy on the ctx's stream in front of the block's first launch, outside any recorded
+ *   range and not part of a recording's key), then the ctx disarms.  The block takes the path of a status raised in its first attraction
+ *   step: nothing is applied, nw_search_end reports the code once and leaves the ctx usable (tests/test_hip_block_status.py).  cap = 0
+ *   disarms; any other code, or a call inside a search, is NW_ERR_BADARG and changes nothing.  a (optional) = int64 out[2]: {the code that
+ *   was armed before this call, 1 if the attraction step runs as a launch of its own (after NW_ERR_HANDOFF or what = 3) else 0}.  The wait
+ *   inside k_nn_wave that raises NW_ERR_HANDOFF by itself is NOT reached this way, and no knob reaches it: that takes a workgroup
+ *   spinning 200 ms for a word that is withheld on purpose. */
 int nw_debug(nw_ctx *ctx, int what, void *a, void *b, int cap, int *n);
 
 /* ---- the block-boundary remesher on the device (ABI 6) ---------------------------------------------------------------------------

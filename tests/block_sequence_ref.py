@@ -12,9 +12,12 @@ A sequence is a list of steps.  A step is a dict:
               ('optimize_layout', None)                 transport only
               ('separate_attraction', BOOL)             transport only
               ('quantum', FACTOR or None)               nw_accumulator_quantum: override = local quantum * FACTOR / dropped (no oracle parameter)
+              ('raise_status', NAME)                    nw_debug(what = 8): the next block starts with that status in its device state
+                                                        (NAME in STATUS_CODES; a plain integer is passed on as it is, 0 disarms)
     search  the block's search() arguments; arrays by NAME in the scene (the same object every time, as a caller that keeps its arrays):
               lams, num_iters, sigma_inv, weights, data, pos, last_step, to_host, regulariser ('I' / 'wfunc': cg.Lfuncs, cg.Lhfuncs)
-    raises  'nan': the block ends in NW_ERR_NAN (AssertionError; the mesh stays at the last good iterate)
+    raises  the block ends in that status: 'nan' (NW_ERR_NAN, AssertionError), 'singular' (NW_ERR_SINGULAR, LinAlgError), 'internal',
+            'handoff' (NanoWrapError with that code); the mesh stays at the last good iterate
     stated  the GPU test states how many recordings the block makes at level 0 (see build())
 
 run_device(steps, level) plays them through ShrinkwrapMeshConjGrad on one NativeContext (level 0: blocks as hipGraphs; 1: every launch
@@ -188,6 +191,18 @@ def nan_case():
     return steps
 
 
+STATUS_CODES = dict(nan=-3, singular=-4, internal=-7, handoff=-9)          # the statuses a kernel of a single-rank block can raise (include/nanowrap.h)
+STATUS_TAIL = 3
+
+
+def status_case(name, early=False):
+    """OPENING identical blocks (1 with `early`), a block that starts with the status `name` armed in its device state (nw_debug(what = 8):
+    the path of a status raised in the first iteration's attraction step), then three more blocks identical to the opening.  Returns
+    (steps, control): control = as many blocks with nothing armed.  The armed block's index is OPENING, or 1 with `early`."""
+    assert name in STATUS_CODES
+    return build([dict(pre=[('raise_status', name)], raises=name)], after=1 if early else OPENING, tail=STATUS_TAIL)
+
+
 EVICTION_REVISITS = 3
 
 
@@ -207,14 +222,26 @@ def _tail(seq, n):
     return np.array(seq[len(seq) - n:] if n else [], 'f4')
 
 
-def run_device(steps, level, mesh0='m3', points0='p6'):
+def status_words(nat, code=0):
+    """nw_debug(what = 8) with `code`: (its return value, the code that was armed before the call, handoff_off)"""
+    out = (ctypes.c_int64 * 2)()
+    rc = nat.L.nw_debug(nat.h, 8, out, None, int(code), None)
+    return rc, int(out[0]), int(out[1])
+
+
+def run_device(steps, level, mesh0='m3', points0='p6', handoff_retries=1):
     """One NativeContext, one TriMesh per mesh name.  Returns (blocks, stats): per block a dict of positions (None with to_host=False),
-    mesh_positions, nearest_face, S, res, tests / ress (this block's entries), loopcount, error, seconds (of search()) and graph_stats() before the block's
-    pre-steps / after the block; stats = graph_stats() after the sequence."""
+    mesh_positions, nearest_face, S, res, tests / ress (this block's entries), loopcount, error (None or the name of the status the block
+    ended in) and message (the exception's text), seconds (of search()) and graph_stats() before the block's
+    pre-steps / after the block; armed = what every 'raise_status' step of the block returned (status_words), status_before /
+    status_info = (the code armed, handoff_off) just before the block's search() and after it; stats = graph_stats() after the sequence.
+    handoff_retries: ShrinkwrapMeshConjGrad.handoff_retries of every optimiser (0: NW_ERR_HANDOFF reaches the caller)."""
     from ch_shrinkwrap_amd.mesh_conj_grad import ShrinkwrapMeshConjGrad, NativeContext
+    from ch_shrinkwrap_amd._lib import NanoWrapError
     sc = scene()
     nat = NativeContext(0)
     meshes = {}
+    names = {v: k for k, v in STATUS_CODES.items()}
 
     def mesh_of(name):
         if name not in meshes:
@@ -224,12 +251,14 @@ def run_device(steps, level, mesh0='m3', points0='p6'):
     def make(mesh_name, reuse, points):
         cg = ShrinkwrapMeshConjGrad(mesh_of(mesh_name), points, native=nat, reuse_device_mesh=reuse)
         cg.set_profiling(level)
+        cg.handoff_retries = handoff_retries
         return cg
 
     cg = make(mesh0, False, sc.get(points0))
     blocks = []
     for st in steps:
         before = cg.graph_stats()
+        armed = []
         for what, arg in st['pre']:
             if what == 'new_cg':
                 cg = make(arg['mesh'], arg['reuse'], cg.points)
@@ -250,22 +279,35 @@ def run_device(steps, level, mesh0='m3', points0='p6'):
                 nat.check(nat.L.nw_accumulator_quantum(nat.h, ctypes.byref(q)))
                 q = ctypes.c_double(q.value * arg if arg else -1.0)
                 nat.check(nat.L.nw_accumulator_quantum(nat.h, ctypes.byref(q)))
+            elif what == 'raise_status':
+                armed.append(status_words(nat, STATUS_CODES.get(arg, arg)))          # (not checked: a refusal is something a test looks at)
             else:
                 raise ValueError(what)
+        _, code_armed, off = status_words(nat, 0)          # the getter disarms: what it found is armed again
+        if code_armed:
+            status_words(nat, code_armed)
+        status_before = (code_armed, off)
         a = st['search']
         cg.Lfuncs, cg.Lhfuncs = [a['regulariser']], [a['regulariser']]
         data = cg.points if a['data'] is None else sc.get(a['data'])
-        n_before, error, out = len(cg.tests), None, None
+        n_before, error, message, out = len(cg.tests), None, None, None
         t0 = time.perf_counter()
         try:
             out = cg.search(data, lams=a['lams'], num_iters=a['num_iters'], weights=sc.get(a['weights']), sigma_inv=sc.get(a['sigma_inv']),
                             pos=a['pos'], last_step=a['last_step'], to_host=a['to_host'])
-        except AssertionError:
-            error = 'nan'
+        except AssertionError as e:
+            error, message = 'nan', str(e)
+        except np.linalg.LinAlgError as e:
+            error, message = 'singular', str(e)
+        except NanoWrapError as e:
+            if e.code not in (STATUS_CODES['internal'], STATUS_CODES['handoff']):
+                raise
+            error, message = names[e.code], str(e)
         seconds = time.perf_counter() - t0
         n = len(cg.tests) - n_before
-        b = dict(seconds=seconds, error=error, loopcount=None if error else cg.loopcount, positions=None if out is None else out.copy(),
-                 mesh_positions=cg.mesh.vertices.copy(), tests=_tail(cg.tests, n), ress=_tail(cg.ress, n), before=before, after=cg.graph_stats())
+        b = dict(seconds=seconds, error=error, message=message, loopcount=None if error else cg.loopcount, positions=None if out is None else out.copy(),
+                 mesh_positions=cg.mesh.vertices.copy(), tests=_tail(cg.tests, n), ress=_tail(cg.ress, n), before=before, after=cg.graph_stats(),
+                 armed=armed, status_before=status_before, status_info=status_words(nat, 0)[1:])
         if error is None:
             b.update(nearest_face=cg.nearest_face.copy(), S=cg.S.copy(), res=cg.res.copy())
         blocks.append(b)
@@ -322,8 +364,8 @@ def run_oracle(steps, mesh0='m3', points0='p6', brute_nn=None):
             elif what == 'refresh_normals':
                 nrm_dev = normals_of(meshes[cur])
                 host_nrm[cur] = nrm_dev.copy()
-            elif what in ('optimize_layout', 'separate_attraction', 'quantum'):
-                pass                                        # transport only / no parameter
+            elif what in ('optimize_layout', 'separate_attraction', 'quantum', 'raise_status'):
+                pass                                        # transport only / no parameter / see below
             else:
                 raise ValueError(what)
         a = st['search']
@@ -331,6 +373,12 @@ def run_oracle(steps, mesh0='m3', points0='p6', brute_nn=None):
         n_before = len(tests)
         b = dict(error=None)
         folded = folded or a['pos']
+        if st['raises'] and any(what == 'raise_status' for what, _ in st['pre']):
+            # a status armed on the device with inputs that are in order: the reference has nothing to raise it from.  It raises before
+            # `self.f[:] = fnew` (mesh_conj_grad.py:514,548,580 vs :288), so the step is left out: positions and history carry over
+            b.update(error=st['raises'], loopcount=None, positions=None, tests=np.zeros(0), ress=np.zeros(0), mesh_positions=m.vertices.copy())
+            blocks.append(b)
+            continue
         try:
             r = O.search(m.vertices.copy(), nrm_dev.copy(), m.neighbor_vertex_table(), m.faces, points, list(a['lams']), a['num_iters'],
                          sc.get(a['sigma_inv']), weights=sc.get(a['weights']), valid=m.valid_vertex_mask(), pos_constraint=a['pos'],

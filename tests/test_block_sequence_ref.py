@@ -55,6 +55,31 @@ def test_oracle_nan_block_leaves_the_mesh_at_the_last_good_iterate():
     assert np.array_equal(blocks[k + 1]['positions'], ref[k]['positions'])
 
 
+@pytest.mark.parametrize('early', [False, True], ids=['late', 'early'])
+def test_oracle_leaves_out_a_block_with_a_status_armed(early):
+    """status_case: the armed block is left out (the reference raises before `self.f[:] = fnew`), so the block after it is, exactly,
+    the block the control runs at the armed index -- for every status alike (the oracle has no parameter for which)."""
+    k = 1 if early else B.OPENING
+    runs = {}
+    for name in ('nan', 'handoff'):
+        steps, control = B.status_case(name, early)
+        assert len(steps) == len(control) == k + 1 + B.STATUS_TAIL
+        assert [s['raises'] for s in steps] == [None] * k + [name] + [None] * B.STATUS_TAIL
+        assert all(s['pre'] == ([('raise_status', name)] if i == k else []) and s['search'] == control[i]['search'] for i, s in enumerate(steps))
+        runs[name] = B.run_oracle(steps)
+    ref = B.run_oracle(control)
+    for name, blocks in runs.items():
+        assert [b['error'] for b in blocks] == [None] * k + [name] + [None] * B.STATUS_TAIL
+        assert np.array_equal(blocks[k]['mesh_positions'], blocks[k - 1]['mesh_positions']) and blocks[k]['positions'] is None
+        for i in range(k):
+            assert np.array_equal(blocks[i]['positions'], ref[i]['positions'])
+        for i in range(k + 1, len(blocks)):          # shifted by the block that was left out: positions, and the `tests` history with them
+            assert blocks[i]['loopcount'] == 3
+            assert np.array_equal(blocks[i]['positions'], ref[i - 1]['positions'])
+            assert np.array_equal(blocks[i]['tests'], ref[i - 1]['tests']) and np.array_equal(blocks[i]['ress'], ref[i - 1]['ress'])
+        assert not np.array_equal(blocks[k + 1]['positions'], blocks[k - 1]['positions'])
+
+
 def test_eviction_sequence_has_more_shapes_than_the_ring_has_slots():
     steps, n = B.eviction_case()
     shapes = [(s['search']['num_iters'], s['search']['pos']) for s in steps[B.OPENING:]]

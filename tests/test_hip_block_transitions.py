@@ -117,23 +117,26 @@ def _expected_recordings(steps):
     return out
 
 
-def _run_levels(name, steps, mesh0='m3', points0='p6'):
-    runs = {lv: B.run_device(steps, lv, mesh0, points0) for lv in LEVELS}
+def _run_levels(name, steps, mesh0='m3', points0='p6', searches=None, **device):
+    """searches: how many calls of nw_search each block makes (one, unless search() runs a block again: tests/test_hip_block_status.py);
+    device: further arguments of run_device"""
+    searches = [1] * len(steps) if searches is None else searches
+    runs = {lv: B.run_device(steps, lv, mesh0, points0, **device) for lv in LEVELS}
     _report(name, steps, runs[0])
     # 1. replay equals direct launches, after every block
     for lv in (1, 4):
         for i, (a, b) in enumerate(zip(runs[0][0], runs[lv][0])):
             assert _same_block(a, b) == [], 'block %d: level 0 and level %d differ in %s' % (i, lv, _same_block(a, b))
     # 2. the replay path ran
-    n = len(steps)
     want = _expected_recordings(steps)
     got = [_delta(b)['captured'] for b in runs[0][0]]
     for i, b in enumerate(runs[0][0]):
         d = _delta(b)
-        assert d['replayed'] == 1 and d['direct'] == 0, 'level 0, block %d was not replayed from a graph: %s' % (i, d)
+        assert d['replayed'] == searches[i] and d['direct'] == 0, 'level 0, block %d was not replayed from a graph: %s' % (i, d)
         assert want[i] is None or d['captured'] == want[i], 'level 0, block %d: recordings per block %s, stated %s' % (i, got, want)
+    n = sum(searches)
     assert runs[1][1] == dict(captured=0, replayed=0, direct=n), runs[1][1]
-    head = sum(1 for st in steps if st['search']['num_iters'] > 1)
+    head = sum(k for st, k in zip(steps, searches) if st['search']['num_iters'] > 1)
     assert runs[4][1]['replayed'] == head and runs[4][1]['direct'] == n - head, runs[4][1]
     return runs
 
