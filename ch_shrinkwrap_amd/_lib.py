@@ -198,6 +198,14 @@ def ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def cloud_f32(points):
+    """-> (what keeps the memory alive, pointer, n, on_device): an (n,3) array (copied to float32 if it is not) or (device pointer, n)"""
+    if isinstance(points, tuple) and len(points) == 2 and isinstance(points[0], (int, np.integer)):
+        return None, ptr(int(points[0])), int(points[1]), 1
+    a = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    return a, ptr(a), a.shape[0], 0
+
+
 class NanoWrapError(RuntimeError):
     def __init__(self, code, msg):
         RuntimeError.__init__(self, 'nanowrap status %d: %s' % (code, msg))

@@ -93,7 +93,8 @@ UNITS = [
     (_csrc('nw_proximity.hip'), OBJ_PROXIMITY, [_include('nw_proximity.h'), _csrc('nw_proximity_core.h'), _csrc('nw_distance_core.h'),
                                                 _csrc('nw_intersections_core.h')] + _BQ_H, _QUERY),
     # what the eleven above share (csrc/nw_bq.h), and the two below them: the exclusive scan, the point grid's bounding box and
-    # counting sort, float and double, and the mesh query units' face grid (its arithmetic is in nw_bq_core.h)
+    # counting sort, float and double, the cloud query units' cloud grid and the mesh query units' face grid (their arithmetic is in
+    # nw_bq_core.h, which nw_neighbours_core.h includes for the cloud point: every unit on that header lists it through _BQ_H)
     (_csrc('nw_bq.hip'), OBJ_BQ, _BQ, _QUERY),
     # localizations mapped onto the mesh: per-vertex mass, per-face counts and value sums as integers (nw_mapping_core.h: the weights, the
     # quantisation, the limbs and the vertex areas, which the tests also compile for the CPU; it includes nw_volume_core.h for the capped
@@ -269,7 +270,6 @@ KERNEL_BUDGETS = {
     'k_lm_totals':                    (32, 96),            # LDS = the four waves' three counters
     # DBSCAN clustering (csrc/nw_clustering.o): one lane per point in cell order, the walk's visitor in registers; zero scratch.  All of them
     # reach 8 waves per SIMD (512 // VGPRs, capped at 8) with room to the next step at 64
-    'k_pc_order':                     (16, 0),
     'k_pc_count':                     (56, 64),            # the point in float64, the walk's ranges and two counters: 8 waves per SIMD; LDS = the four waves' two counters
     'k_pc_hook':                      (56, 64),            # the same walk and the two roots of a union: 8 waves per SIMD
     'k_pc_compress':                  (16, 0),
@@ -278,7 +278,6 @@ KERNEL_BUDGETS = {
     'k_pc_stats':                     (40, 96),            # eight values through the wave's butterflies: 8 waves per SIMD; LDS = the four waves' three counters
     'k_pc_totals':                    (64, 256),           # eight 64-bit sums per thread, one workgroup: 8 waves per SIMD; LDS = the four waves' eight counters
     # pair-distance counts (csrc/nw_pairs.o): one lane per query, its counters in a column of LDS, no atomics on the results; zero scratch
-    'k_pq_order':                     (16, 0),
     'k_pq_pairs<false>':              (56, 8 * 1024),      # up to 16 bins: 128 lanes x 16 bins x 4 bytes; the edges are scalar operands
     'k_pq_pairs<true>':               (56, 17 * 1024),     # up to 64 bins: 64 lanes x 64 bins x 4 bytes and the LDS copy of the edges (512 bytes)
     'k_pq_totals':                    (24, 2048),          # LDS = one 64-bit sum per thread
@@ -304,7 +303,6 @@ KERNEL_BUDGETS = {
     'k_sk_vertex':                    (16, 0),
     # the local shape of the cloud (csrc/nw_structure.o): one lane per query, its ten 64-bit sums in registers, no atomics on the results;
     # zero scratch
-    'k_st_order':                     (8, 0),
     'k_st_moments':                   (64, 64),            # the query in float64, the walk's ranges, ten 64-bit sums (62 VGPRs): 8 waves per SIMD; LDS = the two waves' four counters
     'k_st_eigen':                     (64, 0),             # six elements of C, nine of V and a rotation in flight, all float64 (60 VGPRs): 8 waves per SIMD
     'k_st_totals':                    (24, 2048),          # LDS = one 64-bit sum per thread
@@ -323,7 +321,9 @@ KERNEL_BUDGETS = {
     'k_sp_residual':                  (16, 32),
     'k_sp_absmax':                    (8, 32),
     'k_sp_field':                     (24, 32),
-    # what the eleven units above share (csrc/nw_bq.o), and nw_mapping.o: the exclusive scan, and the point grid of hole punching (f32) and of the metric (f64)
+    # what the eleven units above share (csrc/nw_bq.o), and nw_mapping.o: the exclusive scan, and the point grid in float (hole punching, and
+    # the cloud grid of the four cloud query units: neighbours, clustering, pairs, local shape -- k_bq_scatter_f32 is their one scatter, a
+    # sorted point carrying its index) and in double (the metric, the face grid)
     'k_bq_scan_tiles':                (32, 1024),
     'k_bq_scan_bsums':                (32, 1024),
     'k_bq_scan_final':                (32, 1024),

@@ -1,11 +1,12 @@
 // What the query units (nw_holepunch.hip, nw_surgery.hip, nw_isosurface.hip, nw_evaluation.hip, nw_simulation.hip) share: the device
 // buffer and the staging of host arrays into it, the base of their contexts with its create / destroy / last_error bodies, the HIP-call
 // macro, the host checks of a mesh and of finiteness, the ordered-key maps, the exclusive scan, the point grid (bounding box, sizing,
-// counting sort by cell, the cell index of a coordinate) in float and in double, the face grid of the six mesh query units (the
+// counting sort by cell, the cell index of a coordinate) in float and in double, the cloud grid of the four cloud query units (the
+// intake of a cloud: the copy, its box, its finiteness; and its binning at a cell size), the face grid of the six mesh query units (the
 // intake of a mesh: centroids, radii, their reduction, the centroids' box; and their binning at a cell size), and the host loop of the
 // 64-bit radix select.  Kernels and host entries are in nw_bq.hip; what needs no HIP is in nw_bq_core.h.  Each C-ABI keeps its own
-// status codes and error texts: everything here that can fail returns a hipError_t, a flag or a FaceStatus, and its user says what that
-// means (face_fail holds the words the six mesh units share; the prefix and the status are the unit's).
+// status codes and error texts: everything here that can fail returns a hipError_t, a flag, a CloudStatus or a FaceStatus, and its user
+// says what that means (cloud_fail and face_fail hold the words the units share; the prefix and the status are the unit's).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -160,11 +161,12 @@ template <class T> struct Grid {
     int64_t cells() const { return (int64_t)dims[0] * dims[1] * dims[2]; }
 };
 
-// the ordered key of a coordinate, and a point in cell order: a float cloud keeps its coordinates only ({x, y, z, 0}), a double cloud also
-// the index in the caller's array
+// the ordered key of a coordinate, and a point in cell order: its coordinates and its index in the caller's array.  The fourth word of
+// a float point is that index as an int, not a float: a kernel that needs the coordinates only may read the point as a float4 and
+// leave .w alone (hole punching, the neighbour unit).
 struct PtF64 { double x, y, z; long long i; };
 template <class T> struct GridOf;
-template <> struct GridOf<float> { typedef int key; typedef float4 point; };
+template <> struct GridOf<float> { typedef int key; typedef PtF32 point; };
 template <> struct GridOf<double> { typedef unsigned long long key; typedef PtF64 point; };
 
 // cell index along one axis: the same expression for binning and for every query
@@ -184,6 +186,76 @@ template <class T> hipError_t bounds(hipStream_t stream, DevBuf &keys, const T *
 // `cursor` are work buffers; the stream is synchronised.
 template <class T> hipError_t build_grid(hipStream_t stream, const T *xyz, int n, const Grid<T> &g, DevBuf &cell, DevBuf &cursor, DevBuf &scan_tmp,
                                          DevBuf &cstart, DevBuf &sorted, int *total);
+
+// ---- cloud grid (nw_bq.hip) -------------------------------------------------------------------------------------------------------------
+// What the cloud query units (nw_neighbours, nw_clustering, nw_pairs, nw_structure) do with a cloud before they walk it: the copy onto
+// the device, its box and finiteness, and the cloud binned into the float point grid, a sorted point carrying its index.
+
+// how taking a cloud in or binning it ended; every C-ABI gives that its own status and its own text (cloud_fail)
+enum CloudCheck {
+    CLOUD_OK = 0,
+    CLOUD_NONFINITE,          // a localization is not finite
+    CLOUD_NO_GRID,            // no cell size keeps the grid within its cap
+    CLOUD_BAD_CELL,           // the cell size is not a positive float
+    CLOUD_BAD_TOTAL,          // the cell counts do not add up to the cloud
+    CLOUD_HIP                 // a HIP call failed: `hip`, and `call` names it
+};
+
+struct CloudStatus {
+    CloudCheck check = CLOUD_OK;
+    hipError_t hip = hipSuccess;
+    const char *call = "";
+    CloudStatus(CloudCheck c = CLOUD_OK) : check(c) {}
+    bool ok() const { return check == CLOUD_OK; }
+};
+
+// the statuses of a C-ABI that a CloudStatus maps to
+struct CloudCodes { int badarg, nonfinite, nomem, hip; };
+
+// a failed CloudStatus as the ABI's status, with "<who>: <what>" in last_error (who = the ABI's function for an intake, its prefix for a
+// binning)
+inline int cloud_fail(Ctx *ctx, const char *who, const CloudStatus &s, const CloudCodes &c)
+{
+    const std::string w = std::string(who) + ": ";
+    switch (s.check) {
+    case CLOUD_NONFINITE: return fail(ctx, c.nonfinite, w + "a localization is not finite");
+    case CLOUD_NO_GRID: return fail(ctx, c.badarg, w + "no cell size keeps the grid within its cap");
+    case CLOUD_BAD_CELL: return fail(ctx, c.badarg, w + "the cell size is not a positive float");
+    case CLOUD_BAD_TOTAL: return fail(ctx, c.hip, w + "the cell counts do not add up to the cloud");
+    default: return fail(ctx, s.hip == hipErrorOutOfMemory ? c.nomem : c.hip, w + s.call + ": " + hipGetErrorString(s.hip));
+    }
+}
+
+// A unit checks its arguments itself, before any HIP call and before it looks at its context: NULL, n, on_device, and the finiteness of
+// a host array.  What a host array with a non-finite value does to a cloud taken in earlier differs between the units and is part of
+// their ABIs: pairs and structure forget() it (a failed call leaves no cloud, whichever check failed), neighbours and clustering
+// return before anything is reset and keep answering from it.
+struct CloudGrid {
+    int n = 0;                    // 0: no cloud
+    Grid<float> g{};              // lo, hi: the cloud's box; h, dims: the grid at hand
+    double h_start = 0.0;         // the cell size the grid at hand was sized from (0: none)
+    DevBuf cloud, mm, cell, cursor, cstart, sorted, scan_tmp;
+
+    void forget() { n = 0; h_start = 0.0; }
+
+    // Takes in xyz[0..3 count) from the host or the device: the copy, its box, and the device's verdict on its finiteness.  The stream
+    // is synchronised: the caller's array is free afterwards.  n stays 0 unless all is well, and the grid at hand is forgotten either
+    // way.
+    CloudStatus set_cloud(hipStream_t stream, const float *xyz, int64_t count, bool on_device);
+
+    // the widest axis of the cloud's box
+    double emax() const
+    {
+        double e = 0.0;
+        for (int d = 0; d < 3; ++d) e = std::max(e, (double)g.hi[d] - (double)g.lo[d]);
+        return e;
+    }
+
+    // The grid for the starting cell size h0 (cloud_cell of the unit's candidate, or the neighbour unit's own rule): the one at hand if
+    // it was sized from the same h0, else the cloud binned anew under CLOUD_GRID_RULE (keep_or_rebin, build_grid: `sorted` holds the
+    // cloud as PtF32 in cell order, cstart the cells' starts), which synchronises the stream once.
+    CloudStatus bin(hipStream_t stream, double h0);
+};
 
 // ---- face grid (nw_bq.hip) --------------------------------------------------------------------------------------------------------------
 // What the mesh query units (nw_distance, nw_intersections, nw_rays, nw_volume, nw_proximity, nw_mapping) do with a mesh before they walk

@@ -2,7 +2,8 @@
 // link time through its host stubs:
 //   k_bq_scan_*                        the exclusive scan: int, three launches, exact (the per-iteration scan of nanowrap.hip is another one)
 //   k_bq_bbox_*                        bounding box (ordered keys, atomicMin / atomicMax) and finiteness of a cloud
-//   k_bq_cell_count_*, k_bq_scatter_*  counting sort of a cloud by cell of its grid, with the scan between them
+//   k_bq_cell_count_*, k_bq_scatter_*  counting sort of a cloud by cell of its grid, with the scan between them; a sorted point carries
+//                                      its index in the caller's array (the one scatter of the four cloud query units)
 //   k_bq_face_setup, k_bq_rho_reduce   the face grid of the mesh query units: a face's float64 centroid and radius, rho_max and the sum
 // The grid's kernels are written once as templates over the coordinate type and wrapped in plain kernels _f32 / _f64:
 // build.kernel_resources names a kernel without its template arguments, so two instantiations of one template would share a budget row.
@@ -139,7 +140,7 @@ template <class T> __device__ __forceinline__ void cell_count_body(const T *__re
 }
 
 // (the one line that differs between the two scatters)
-__device__ __forceinline__ float4 point_of(const float *p, int) { return make_float4(p[0], p[1], p[2], 0.0f); }
+__device__ __forceinline__ bq::PtF32 point_of(const float *p, int i) { return {p[0], p[1], p[2], i}; }
 __device__ __forceinline__ bq::PtF64 point_of(const double *p, int i) { return {p[0], p[1], p[2], i}; }
 
 template <class T> __device__ __forceinline__ void scatter_body(const T *__restrict__ xyz, int n, const int *__restrict__ cell, int *__restrict__ cursor,
@@ -158,7 +159,7 @@ __global__ __launch_bounds__(BQ_BLOCK) void k_bq_bbox_f32(const float *__restric
 __global__ __launch_bounds__(BQ_BLOCK) void k_bq_bbox_f64(const double *__restrict__ xyz, int n, unsigned long long *__restrict__ mm) { bbox_body(xyz, n, mm); }
 __global__ __launch_bounds__(BQ_BLOCK) void k_bq_cell_count_f32(const float *__restrict__ xyz, int n, bq::Grid<float> g, int *__restrict__ cell, int *__restrict__ count) { cell_count_body(xyz, n, g, cell, count); }
 __global__ __launch_bounds__(BQ_BLOCK) void k_bq_cell_count_f64(const double *__restrict__ xyz, int n, bq::Grid<double> g, int *__restrict__ cell, int *__restrict__ count) { cell_count_body(xyz, n, g, cell, count); }
-__global__ __launch_bounds__(BQ_BLOCK) void k_bq_scatter_f32(const float *__restrict__ xyz, int n, const int *__restrict__ cell, int *__restrict__ cursor, float4 *__restrict__ sorted) { scatter_body(xyz, n, cell, cursor, sorted); }
+__global__ __launch_bounds__(BQ_BLOCK) void k_bq_scatter_f32(const float *__restrict__ xyz, int n, const int *__restrict__ cell, int *__restrict__ cursor, bq::PtF32 *__restrict__ sorted) { scatter_body(xyz, n, cell, cursor, sorted); }
 __global__ __launch_bounds__(BQ_BLOCK) void k_bq_scatter_f64(const double *__restrict__ xyz, int n, const int *__restrict__ cell, int *__restrict__ cursor, bq::PtF64 *__restrict__ sorted) { scatter_body(xyz, n, cell, cursor, sorted); }
 
 // the kernels of a coordinate type
@@ -214,6 +215,44 @@ template hipError_t bq::bounds<float>(hipStream_t, DevBuf &, const float *, int,
 template hipError_t bq::bounds<double>(hipStream_t, DevBuf &, const double *, int, const double *, int, Grid<double> *, bool[2]);
 template hipError_t bq::build_grid<float>(hipStream_t, const float *, int, const Grid<float> &, DevBuf &, DevBuf &, DevBuf &, DevBuf &, DevBuf &, int *);
 template hipError_t bq::build_grid<double>(hipStream_t, const double *, int, const Grid<double> &, DevBuf &, DevBuf &, DevBuf &, DevBuf &, DevBuf &, int *);
+
+// ---- cloud grid -------------------------------------------------------------------------------------------------------------------------
+// (returns the CloudStatus of a failed HIP call with the call's text)
+#define BQ_CLOUD_TRY(expr)                                                                                     \
+    do {                                                                                                       \
+        const hipError_t e_ = (expr);                                                                          \
+        if (e_ != hipSuccess) { CloudStatus s_(CLOUD_HIP); s_.hip = e_; s_.call = #expr; return s_; }          \
+    } while (0)
+
+bq::CloudStatus bq::CloudGrid::set_cloud(hipStream_t stream, const float *xyz, int64_t count, bool on_device)
+{
+    forget();
+    BQ_CLOUD_TRY(cloud.ensure(sizeof(float) * 3 * (size_t)count));
+    BQ_CLOUD_TRY(hipMemcpyAsync(cloud.p, xyz, sizeof(float) * 3 * (size_t)count, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+    bool finite[2];
+    BQ_CLOUD_TRY(bounds<float>(stream, mm, cloud.as<float>(), (int)count, nullptr, 0, &g, finite));
+    if (!finite[0]) return CLOUD_NONFINITE;
+    n = (int)count;
+    return CLOUD_OK;
+}
+
+bq::CloudStatus bq::CloudGrid::bin(hipStream_t stream, double h0)
+{
+    const double ext[3] = {(double)g.hi[0] - (double)g.lo[0], (double)g.hi[1] - (double)g.lo[1], (double)g.hi[2] - (double)g.lo[2]};
+    double h = 0.0;
+    const Bins b = keep_or_rebin(CLOUD_GRID_RULE, n, ext, h0, &h_start, &h, g.dims);
+    if (b == BINS_KEPT) return CLOUD_OK;
+    if (b == BINS_NONE) return CLOUD_NO_GRID;
+    // the float the kernels divide by (dims were counted with the double: a cell index that the rounding pushes past them is clamped
+    // into the last cell, as every cell index is, which only brings its points into an earlier ring)
+    g.h = (float)h;
+    if (!(g.h > 0.0f) || !std::isfinite(g.h)) return CLOUD_BAD_CELL;
+    int total = -1;
+    BQ_CLOUD_TRY(build_grid<float>(stream, cloud.as<float>(), n, g, cell, cursor, scan_tmp, cstart, sorted, &total));
+    if (total != n) return CLOUD_BAD_TOTAL;
+    h_start = h0;
+    return CLOUD_OK;
+}
 
 // ---- face grid --------------------------------------------------------------------------------------------------------------------------
 // one thread per face: the float64 centroid and rho_f, a hair enlarged so that rounding can only make a bound weaker
@@ -294,9 +333,9 @@ bq::FaceStatus bq::FaceGrid::set_faces(hipStream_t stream, const float *pos, int
 bq::FaceStatus bq::FaceGrid::bin(hipStream_t stream, double h0)
 {
     const double ext[3] = {g.hi[0] - g.lo[0], g.hi[1] - g.lo[1], g.hi[2] - g.lo[2]};
-    const FaceBins b = face_bins(nf, ext, h0, &h_start, &g.h, g.dims);
-    if (b == FACE_BINS_KEPT) return FACES_OK;
-    if (b == FACE_BINS_NONE) return FACES_NO_GRID;
+    const Bins b = face_bins(nf, ext, h0, &h_start, &g.h, g.dims);
+    if (b == BINS_KEPT) return FACES_OK;
+    if (b == BINS_NONE) return FACES_NO_GRID;
     int total = -1;
     BQ_FACE_TRY(build_grid<double>(stream, cen.as<double>(), nf, g, cell, ccount, scan_tmp, cstart, sorted, &total));
     if (total != nf) return FACES_BAD_TOTAL;

@@ -1,7 +1,8 @@
-// The part of nw_bq.h that needs no HIP: the sizing of a point grid, the mesh query units' face grid (a face's centroid and radius, the
-// cell size, when to bin anew) and the walk of a radix select.  The query units get it through nw_bq.h, and nw_distance_core.h and
-// nw_intersections_core.h include it for the centroid; tests/test_bq_core_cpu.py compiles it for the CPU with g++.  Without a HIP
-// compiler BQ_HD is plain `inline`.
+// The part of nw_bq.h that needs no HIP: the sizing of a point grid and when to bin anew, the cloud query units' cloud grid (the point in
+// cell order, the limits, the cell size), the mesh query units' face grid (a face's centroid and radius, the cell size) and the walk of
+// a radix select.  The query units get it through nw_bq.h, nw_distance_core.h and nw_intersections_core.h include it for the centroid
+// and nw_neighbours_core.h for the point; tests/test_bq_core_cpu.py compiles it for the CPU with g++.  Without a HIP compiler BQ_HD is
+// plain `inline`.
 #pragma once
 #include <cstdint>
 #include <cmath>
@@ -39,6 +40,39 @@ inline bool size_grid(const GridRule &rule, int64_t n, const double ext[3], doub
         *h *= 1.1;
     }
     return (int64_t)dims[0] * dims[1] * dims[2] <= cap;
+}
+
+// The sizing half of CloudGrid::bin and FaceGrid::bin (nw_bq.h).  *h_start = the cell size the grid at hand was sized from (0: there is
+// none).  A grid sized from the same h0 is kept; else *h_start = 0 and h, dims are sized anew from h0 under `rule`, and the caller sets
+// *h_start = h0 once it has binned.
+enum Bins { BINS_KEPT = 0, BINS_NEW = 1, BINS_NONE = 2 };      // NONE: no cell size keeps the grid within its cap
+
+inline Bins keep_or_rebin(const GridRule &rule, int64_t n, const double ext[3], double h0, double *h_start, double *h, int dims[3])
+{
+    if (*h_start == h0) return BINS_KEPT;
+    *h_start = 0.0;
+    *h = h0;
+    return size_grid(rule, n, ext, h, dims) ? BINS_NEW : BINS_NONE;
+}
+
+// ---- the cloud grid of the cloud query units (neighbours, clustering, pairs, local shape) -------------------------------------------------
+// a cloud point in cell order: its float coordinates and its index in the caller's array (GridOf<float>::point of nw_bq.h)
+struct alignas(16) PtF32 {
+    float x, y, z;
+    int i;
+};
+
+// at most max(2 n, 65536) cells, up to 2^26; at most 1025 an axis (NWK_CELL_SLACK rests on it); 400 widening steps
+const GridRule CLOUD_GRID_RULE = {2, 1ll << 26, 1025, 400};
+
+// The cell size a cloud grid starts from: the unit's candidate (a fraction of eps, of the largest radius, of the radius), never below a
+// 1024th of the widest axis of the cloud's box (emax), so that no cell index is clamped but by its rounding: the walks' proofs need it.
+// A cell size that is no positive finite float gives way to the extent, and a cloud without extent gets one cell of side 1.
+inline double cloud_cell(double candidate, double emax)
+{
+    double h = std::max(candidate, emax / 1024.0);
+    if (!((float)h > 0.0f) || !std::isfinite((float)h)) h = (emax > 0.0 && std::isfinite((float)emax)) ? emax : 1.0;
+    return h;
 }
 
 // ---- the face grid of the mesh query units: a face's ball, the cell size, the decision to bin -------------------------------------------
@@ -81,16 +115,10 @@ inline double face_cell(double candidate, double emax)
 // four rings, a few hundred cell ranges
 inline double band_cell(double rho_mean, double rho_max, double d_cap) { return std::max(2.0 * rho_mean, (d_cap + rho_max) / 2.0); }
 
-// The sizing half of FaceGrid::bin (nw_bq.h).  *h_start = the cell size the grid at hand was sized from (0: there is none).  A grid sized
-// from the same h0 is kept; else *h_start = 0 and h, dims are sized anew from h0, and the caller sets *h_start = h0 once it has binned.
-enum FaceBins { FACE_BINS_KEPT = 0, FACE_BINS_NEW = 1, FACE_BINS_NONE = 2 };      // NONE: no cell size keeps the grid within its cap
-
-inline FaceBins face_bins(int64_t nf, const double ext[3], double h0, double *h_start, double *h, int dims[3])
+// FaceGrid::bin's decision: keep_or_rebin under FACE_GRID_RULE
+inline Bins face_bins(int64_t nf, const double ext[3], double h0, double *h_start, double *h, int dims[3])
 {
-    if (*h_start == h0) return FACE_BINS_KEPT;
-    *h_start = 0.0;
-    *h = h0;
-    return size_grid(FACE_GRID_RULE, nf, ext, h, dims) ? FACE_BINS_NEW : FACE_BINS_NONE;
+    return keep_or_rebin(FACE_GRID_RULE, nf, ext, h0, h_start, h, dims);
 }
 
 // ---- radix select over 64-bit keys, a byte per pass from the top ------------------------------------------------------------------------

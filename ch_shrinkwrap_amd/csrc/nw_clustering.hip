@@ -1,8 +1,7 @@
 // Exact DBSCAN clustering of a localization cloud on the device (MI355X, gfx950): include/nw_clustering.h.
 //
-//   (bq::bounds, bq::size_grid, bq::build_grid)   the query units' shared point grid in float: bounding box and finiteness of the cloud,
-//                                     cell of every point and the cells' starts
-//   k_pc_order       the cloud in cell order with every point's index in the caller's array (the shared scatter keeps coordinates only)
+//   (bq::CloudGrid: set_cloud, bin)   the cloud query units' shared cloud grid in float (nw_bq.h): bounding box and finiteness of the
+//                                     cloud, the cloud in cell order with every point's index in the caller's array, the cells' starts
 //   k_pc_count       one lane per point, in cell order: the ring walk up to count_cap -> count, core; shortcut (a)
 //   k_pc_hook        one lane per core point: union with every core point near it that has a smaller index, as k_ws_hook does it (find
 //                    both roots, CAS the larger onto the smaller, climb from what is found on failure); shortcut (b): a cell's core
@@ -14,7 +13,7 @@
 //   k_pc_totals      the blocks' counters, one workgroup, a fixed order
 //
 // The definition -- near, the walk, the guard of the shortcuts, the three visitors -- is csrc/nw_clustering_core.h, which the tests also
-// compile for the CPU.  The device buffer, the point grid and the context's scaffolding are the query units' shared ones (nw_bq.h).
+// compile for the CPU.  The device buffer, the cloud grid and the context's scaffolding are the query units' shared ones (nw_bq.h).
 // All stores are vector stores; no kernel uses scratch (build.py's KERNEL_BUDGETS checks it).
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -72,18 +71,6 @@ __device__ __forceinline__ void pc_block_counters(i64 a, i64 b, int col_a, int c
         for (int w = 0; w < NWP_WAVES; ++w) s += s_w[w][threadIdx.x];
         partial[(int64_t)blockIdx.x * NWP_PARTIALS + (threadIdx.x == 0 ? col_a : col_b)] = s;
     }
-}
-
-__global__ __launch_bounds__(NWP_BLOCK) void k_pc_order(const float *__restrict__ xyz, int n, const int *__restrict__ cell, int *__restrict__ cursor,
-                                                        nwp_pt *__restrict__ pts)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int slot = atomicAdd(&cursor[cell[i]], 1);          // (order inside a cell is arbitrary: no output depends on it)
-    if (slot < 0 || slot >= n) return;                        // (cannot happen: the cursors start at the scan of the counts)
-    nwp_pt p;
-    p.x = xyz[3 * (int64_t)i]; p.y = xyz[3 * (int64_t)i + 1]; p.z = xyz[3 * (int64_t)i + 2]; p.i = i;
-    pts[slot] = p;
 }
 
 // cell_min[c] = the smallest index among the core points of cell c (read by k_pc_hook, shortcut (b)); parent[i] = i
@@ -331,12 +318,7 @@ using bq::DevBuf;
 using bq::fail;
 
 struct nwp_ctx : bq::Ctx {
-    // the cloud (nwp_set_cloud) and its box
-    int n = 0;
-    DevBuf cloud, mm;
-    bq::Grid<float> g{};
-    double h_start = 0.0;               // the cell size the grid at hand was sized from (0: none)
-    DevBuf cell, cursor, cstart, sorted, scan_tmp, pts;
+    bq::CloudGrid grid;                 // the cloud (nwp_set_cloud), its box and its cells
     bool shortcuts = true;
     // one query
     DevBuf count, core, core_sorted, parent, cell_min, root, is_root, rank, label, anchor, partial, totals;
@@ -349,47 +331,12 @@ namespace {
 
 #define NWP_HIP(call) BQ_HIP(call, NWP_ERR_NOMEM, NWP_ERR_HIP)
 
-// at most max(2 n, 65536) cells, up to 2^26; at most 1025 an axis (NWK_CELL_SLACK rests on it); 400 widening steps
-const bq::GridRule NWP_GRID_RULE = {2, 1ll << 26, 1025, 400};
+const bq::CloudCodes NWP_CODES = {NWP_ERR_BADARG, NWP_ERR_NONFINITE, NWP_ERR_NOMEM, NWP_ERR_HIP};
 
 inline int nblk(int64_t n) { return bq::nblk(n, NWP_BLOCK); }
 
-// the cell size a query starts from: NWP_CELL_OF_EPS of eps, never below 1/1024 of the widest axis (so that no cell index is clamped but
-// by its rounding: the guard's proof needs it)
-double starting_cell(const nwp_ctx *ctx, double eps)
-{
-    double emax = 0.0;
-    for (int d = 0; d < 3; ++d) emax = std::max(emax, (double)ctx->g.hi[d] - (double)ctx->g.lo[d]);
-    double h = std::max(NWP_CELL_OF_EPS * eps, emax / 1024.0);
-    if (!((float)h > 0.0f) || !std::isfinite((float)h)) h = (emax > 0.0 && std::isfinite((float)emax)) ? emax : 1.0;
-    return h;
-}
-
-// the grid for a query with this eps: the one at hand if it was sized from the same starting cell, else the cloud binned anew
-int ensure_grid(nwp_ctx *ctx, double eps)
-{
-    const double h0 = starting_cell(ctx, eps);
-    if (ctx->h_start == h0) return NWP_OK;
-    ctx->h_start = 0.0;
-    double ext[3];
-    for (int d = 0; d < 3; ++d) ext[d] = (double)ctx->g.hi[d] - (double)ctx->g.lo[d];
-    double h = h0;
-    if (!bq::size_grid(NWP_GRID_RULE, ctx->n, ext, &h, ctx->g.dims)) return fail(ctx, NWP_ERR_BADARG, "nwp: no cell size keeps the grid within its cap");
-    ctx->g.h = (float)h;
-    if (!(ctx->g.h > 0.0f) || !std::isfinite(ctx->g.h)) return fail(ctx, NWP_ERR_BADARG, "nwp: the cell size is not a positive float");
-    int total = -1;
-    NWP_HIP(bq::build_grid<float>(ctx->stream, ctx->cloud.as<float>(), ctx->n, ctx->g, ctx->cell, ctx->cursor, ctx->scan_tmp, ctx->cstart, ctx->sorted, &total));
-    if (total != ctx->n) return fail(ctx, NWP_ERR_HIP, "nwp: the cell counts do not add up to the cloud");
-    // the same order once more, with the indices
-    NWP_HIP(ctx->pts.ensure(sizeof(nwp_pt) * (size_t)ctx->n));
-    NWP_HIP(hipMemcpyAsync(ctx->cursor.p, ctx->cstart.p, sizeof(int) * (size_t)ctx->g.cells(), hipMemcpyDeviceToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_pc_order, dim3(nblk(ctx->n)), dim3(NWP_BLOCK), 0, ctx->stream, ctx->cloud.as<float>(), ctx->n, ctx->cell.as<int>(), ctx->cursor.as<int>(),
-                       ctx->pts.as<nwp_pt>());
-    NWP_HIP(hipGetLastError());
-    NWP_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->h_start = h0;
-    return NWP_OK;
-}
+// the cell size a query starts from: NWP_CELL_OF_EPS of eps (bq::cloud_cell)
+double starting_cell(const nwp_ctx *ctx, double eps) { return bq::cloud_cell(NWP_CELL_OF_EPS * eps, ctx->grid.emax()); }
 
 }  // namespace
 
@@ -407,16 +354,9 @@ NWP_EXPORT int nwp_set_cloud(nwp_ctx *ctx, const float *xyz, int64_t n, int on_d
     if (!on_device && !bq::all_finite(xyz, 3 * n)) return fail(ctx, NWP_ERR_NONFINITE, "nwp_set_cloud: a localization is not finite");
     if (!ctx) return NWP_ERR_BADARG;
     NWP_HIP(hipSetDevice(ctx->device));
-    ctx->n = 0;
-    ctx->h_start = 0.0;
     ctx->n_clusters = -1;
-    NWP_HIP(ctx->cloud.ensure(sizeof(float) * 3 * (size_t)n));
-    NWP_HIP(hipMemcpyAsync(ctx->cloud.p, xyz, sizeof(float) * 3 * (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-    bool finite[2];
-    NWP_HIP(bq::bounds<float>(ctx->stream, ctx->mm, ctx->cloud.as<float>(), (int)n, nullptr, 0, &ctx->g, finite));
-    if (!finite[0]) return fail(ctx, NWP_ERR_NONFINITE, "nwp_set_cloud: a localization is not finite");
-    ctx->n = (int)n;
-    return NWP_OK;
+    const bq::CloudStatus s = ctx->grid.set_cloud(ctx->stream, xyz, n, on_device != 0);
+    return s.ok() ? NWP_OK : bq::cloud_fail(ctx, "nwp_set_cloud", s, NWP_CODES);
 }
 
 NWP_EXPORT int nwp_set_shortcuts(nwp_ctx *ctx, int on)
@@ -431,16 +371,16 @@ NWP_EXPORT int nwp_dbscan(nwp_ctx *ctx, double eps, int64_t min_points, int64_t 
 {
     if (!n_clusters || !info || !nwp_args_ok(eps, min_points, count_cap)) return NWP_ERR_BADARG;
     if (!ctx) return NWP_ERR_BADARG;
-    if (ctx->n < 1) return fail(ctx, NWP_ERR_NOCLOUD, "nwp_dbscan: nwp_set_cloud first");
+    if (ctx->grid.n < 1) return fail(ctx, NWP_ERR_NOCLOUD, "nwp_dbscan: nwp_set_cloud first");
     NWP_HIP(hipSetDevice(ctx->device));
     ctx->n_clusters = -1;
-    const int r = ensure_grid(ctx, eps);
-    if (r != NWP_OK) return r;
-    const int n = ctx->n, nb = nblk(n);
-    const int64_t ncell = ctx->g.cells();
+    const bq::CloudStatus binned = ctx->grid.bin(ctx->stream, starting_cell(ctx, eps));
+    if (!binned.ok()) return bq::cloud_fail(ctx, "nwp", binned, NWP_CODES);
+    const int n = ctx->grid.n, nb = nblk(n);
+    const int64_t ncell = ctx->grid.g.cells();
     pc_grid G;
-    G.g = ctx->g;
-    G.h = (double)ctx->g.h;
+    G.g = ctx->grid.g;
+    G.h = (double)ctx->grid.g.h;
     const double eps2 = eps * eps;
     const int shortcuts = (ctx->shortcuts && nwp_shortcuts_ok(G.h, eps)) ? 1 : 0;
     hipStream_t st = ctx->stream;
@@ -460,8 +400,8 @@ NWP_EXPORT int nwp_dbscan(nwp_ctx *ctx, double eps, int64_t min_points, int64_t 
     NWP_HIP(hipMemsetAsync(ctx->partial.p, 0, sizeof(i64) * NWP_PARTIALS * (size_t)nb, st));
     if (shortcuts) NWP_HIP(hipMemsetD32Async((hipDeviceptr_t)ctx->cell_min.p, INT_MAX, (size_t)ncell, st));
 
-    const nwp_pt *pts = ctx->pts.as<nwp_pt>();
-    const int *cstart = ctx->cstart.as<int>();
+    const nwp_pt *pts = ctx->grid.sorted.as<nwp_pt>();
+    const int *cstart = ctx->grid.cstart.as<int>();
     hipLaunchKernelGGL(k_pc_count, dim3(nb), dim3(NWP_BLOCK), 0, st, pts, cstart, G, n, eps2, (int)min_points, (int)count_cap, shortcuts, ctx->count.as<int>(),
                        ctx->core.as<unsigned char>(), ctx->core_sorted.as<unsigned char>(), ctx->parent.as<int>(), ctx->cell_min.as<int>(), ctx->partial.as<i64>());
     hipLaunchKernelGGL(k_pc_hook, dim3(nb), dim3(NWP_BLOCK), 0, st, pts, cstart, G, n, eps2, shortcuts, ctx->core_sorted.as<unsigned char>(),
@@ -470,7 +410,7 @@ NWP_EXPORT int nwp_dbscan(nwp_ctx *ctx, double eps, int64_t min_points, int64_t 
                        ctx->is_root.as<int>());
     NWP_HIP(hipGetLastError());
     int C = -1;
-    NWP_HIP(bq::scan_total(st, ctx->is_root.as<int>(), n, ctx->rank.as<int>(), ctx->scan_tmp, &C));
+    NWP_HIP(bq::scan_total(st, ctx->is_root.as<int>(), n, ctx->rank.as<int>(), ctx->grid.scan_tmp, &C));
     if (C < 0 || C > n) return fail(ctx, NWP_ERR_HIP, "nwp_dbscan: the roots do not add up");
     hipLaunchKernelGGL(k_pc_number, dim3(nb), dim3(NWP_BLOCK), 0, st, n, ctx->root.as<int>(), ctx->rank.as<int>(), ctx->label.as<int>(), ctx->anchor.as<int>());
     hipLaunchKernelGGL(k_pc_border, dim3(nb), dim3(NWP_BLOCK), 0, st, pts, cstart, G, n, eps2, ctx->core_sorted.as<unsigned char>(), ctx->root.as<int>(),
@@ -489,7 +429,7 @@ NWP_EXPORT int nwp_dbscan(nwp_ctx *ctx, double eps, int64_t min_points, int64_t 
     NWP_HIP(hipMemsetD32Async((hipDeviceptr_t)ctx->lo.p, INT_MAX, 3 * Cb, st));
     NWP_HIP(hipMemsetD32Async((hipDeviceptr_t)ctx->hi.p, INT_MIN, 3 * Cb, st));
     pc_acc acc = {ctx->size.as<u64>(), ctx->n_core.as<u64>(), ctx->first.as<int>(), ctx->lo.as<int>(), ctx->hi.as<int>()};
-    hipLaunchKernelGGL(k_pc_stats, dim3(nb), dim3(NWP_BLOCK), 0, st, ctx->cloud.as<float>(), ctx->label.as<int>(), ctx->core.as<unsigned char>(), n, acc,
+    hipLaunchKernelGGL(k_pc_stats, dim3(nb), dim3(NWP_BLOCK), 0, st, ctx->grid.cloud.as<float>(), ctx->label.as<int>(), ctx->core.as<unsigned char>(), n, acc,
                        ctx->partial.as<i64>());
     hipLaunchKernelGGL(k_pc_totals, dim3(1), dim3(NWP_BLOCK), 0, st, ctx->partial.as<i64>(), (int64_t)nb, ctx->totals.as<i64>());
     NWP_HIP(hipGetLastError());

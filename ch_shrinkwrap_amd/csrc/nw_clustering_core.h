@@ -18,11 +18,8 @@
 // that a grid that was not widened has both shortcuts.  The walk then ends before ring 3 ((3 - 1 - 2^-10) 0.57 > 1): 125 cells at most.
 #define NWP_CELL_OF_EPS 0.57
 
-// a cloud point in cell order: its coordinates and its index in the caller's array
-struct alignas(16) nwp_pt {
-    float x, y, z;
-    int i;
-};
+// a cloud point in cell order: its coordinates and its index in the caller's array (the cloud grid's, nw_bq_core.h)
+typedef bq::PtF32 nwp_pt;
 
 // whether the three numbers are a query (a nan fails every comparison)
 NWK_HD bool nwp_args_ok(double eps, long long min_points, long long count_cap)

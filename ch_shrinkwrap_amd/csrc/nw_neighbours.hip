@@ -1,7 +1,8 @@
 // The exact k-th-nearest-neighbour distance on the device (MI355X, gfx950): include/nw_neighbours.h.
 //
-//   (bq::bounds, bq::size_grid, bq::build_grid)   the query units' shared point grid in float: bounding box and finiteness of the cloud,
-//                                     counting sort of the cloud by cell
+//   (bq::CloudGrid: set_cloud, bin)   the cloud query units' shared cloud grid in float (nw_bq.h): bounding box and finiteness of the
+//                                     cloud, counting sort of the cloud by cell (the walks read a sorted point's coordinates as a
+//                                     float4 and leave its fourth word, the index, alone)
 //   k_kn_queries     one lane per query of a list: the ring walk of kn_walk, the result as a double
 //   k_kn_nodes       one lane per node of a voxel lattice, lanes along x: the same walk, the result quantised into the uint64 field
 //
@@ -11,8 +12,8 @@
 // are), with the running maximum and its slot in registers (nwk_list, csrc/nw_neighbours_core.h).  128 lanes x 32 slots x 8 bytes =
 // 32 KB a workgroup.  A list indexed at run time in registers would go to scratch; LDS takes the index as an address.
 //
-// The device buffer with its staging, the point grid and the context's scaffolding are the query units' shared ones (nw_bq.h); what is
-// this unit's own about the grid is its starting cell size and its limits (NWK_GRID_RULE).
+// The device buffer with its staging, the cloud grid and the context's scaffolding are the query units' shared ones (nw_bq.h); what is
+// this unit's own about the grid is its starting cell size, and that the cloud is binned as soon as it is set.
 // All stores are vector stores; no kernel uses scratch (build.py's KERNEL_BUDGETS checks it).
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -123,12 +124,7 @@ using bq::fail;
 using bq::nblk;
 
 struct nwk_ctx : bq::Ctx {
-    // the cloud (nwk_set_cloud) and its box
-    int n = 0;
-    DevBuf cloud, mm;
-    bq::Grid<float> g{};
-    double h_start = 0.0;               // the cell size the grid at hand was sized from (0: none)
-    DevBuf cell, ccount, cstart, sorted, scan_tmp;
+    bq::CloudGrid grid;                 // the cloud (nwk_set_cloud), its box and its cells
     // the queries
     DevBuf q, dist, flag;
     // the node field
@@ -140,8 +136,7 @@ namespace {
 
 #define NWK_HIP(call) BQ_HIP(call, NWK_ERR_NOMEM, NWK_ERR_HIP)
 
-// at most max(2 n, 65536) cells, up to 2^26; at most 1025 an axis (NWK_CELL_SLACK rests on it); 400 widening steps
-const bq::GridRule NWK_GRID_RULE = {2, 1ll << 26, 1025, 400};
+const bq::CloudCodes NWK_CODES = {NWK_ERR_BADARG, NWK_ERR_NONFINITE, NWK_ERR_NOMEM, NWK_ERR_HIP};
 
 bool k_and_cap_ok(int k, double r_cap) { return k >= 1 && k <= NWK_MAX_K && r_cap > 0.0; }             // (a nan cap fails the comparison)
 
@@ -150,10 +145,10 @@ bool k_and_cap_ok(int k, double r_cap) { return k >= 1 && k <= NWK_MAX_K && r_ca
 double starting_cell(const nwk_ctx *ctx, double r_cap)
 {
     double ext[3], emax = 0.0;
-    for (int d = 0; d < 3; ++d) { ext[d] = (double)ctx->g.hi[d] - (double)ctx->g.lo[d]; emax = std::max(emax, ext[d]); }
+    for (int d = 0; d < 3; ++d) { ext[d] = (double)ctx->grid.g.hi[d] - (double)ctx->grid.g.lo[d]; emax = std::max(emax, ext[d]); }
     if (!(emax > 0.0)) return 1.0;
     double h = std::isfinite(r_cap) ? r_cap / 4.0
-                                    : std::cbrt(std::max(ext[0], 1e-3 * emax) * std::max(ext[1], 1e-3 * emax) * std::max(ext[2], 1e-3 * emax) / ctx->n);
+                                    : std::cbrt(std::max(ext[0], 1e-3 * emax) * std::max(ext[1], 1e-3 * emax) * std::max(ext[2], 1e-3 * emax) / ctx->grid.n);
     h = std::max(h, emax / 1024.0);
     if (!(h > 0.0) || !std::isfinite(h)) h = emax;
     return h;
@@ -162,22 +157,8 @@ double starting_cell(const nwk_ctx *ctx, double r_cap)
 // the grid for a query with this cap: the one at hand if it was sized from the same starting cell, else the cloud binned anew
 int ensure_grid(nwk_ctx *ctx, double r_cap)
 {
-    const double h0 = starting_cell(ctx, r_cap);
-    if (ctx->h_start == h0) return NWK_OK;
-    ctx->h_start = 0.0;
-    double ext[3];
-    for (int d = 0; d < 3; ++d) ext[d] = (double)ctx->g.hi[d] - (double)ctx->g.lo[d];
-    double h = h0;
-    if (!bq::size_grid(NWK_GRID_RULE, ctx->n, ext, &h, ctx->g.dims)) return fail(ctx, NWK_ERR_BADARG, "nwk: no cell size keeps the grid within its cap");
-    // the float the kernels divide by (dims were counted with the double: a cell index that the rounding pushes past them is clamped
-    // into the last cell, as every cell index is, which only brings its points into an earlier ring)
-    ctx->g.h = (float)h;
-    if (!(ctx->g.h > 0.0f) || !std::isfinite(ctx->g.h)) return fail(ctx, NWK_ERR_BADARG, "nwk: the cell size is not a positive float");
-    int total = -1;
-    NWK_HIP(bq::build_grid<float>(ctx->stream, ctx->cloud.as<float>(), ctx->n, ctx->g, ctx->cell, ctx->ccount, ctx->scan_tmp, ctx->cstart, ctx->sorted, &total));
-    if (total != ctx->n) return fail(ctx, NWK_ERR_HIP, "nwk: the cell counts do not add up to the cloud");
-    ctx->h_start = h0;
-    return NWK_OK;
+    const bq::CloudStatus s = ctx->grid.bin(ctx->stream, starting_cell(ctx, r_cap));
+    return s.ok() ? NWK_OK : bq::cloud_fail(ctx, "nwk", s, NWK_CODES);
 }
 
 }  // namespace
@@ -196,16 +177,10 @@ NWK_EXPORT int nwk_set_cloud(nwk_ctx *ctx, const float *xyz, int64_t n, int on_d
     if (!on_device && !bq::all_finite(xyz, 3 * n)) return fail(ctx, NWK_ERR_NONFINITE, "nwk_set_cloud: a localization is not finite");
     if (!ctx) return NWK_ERR_BADARG;
     NWK_HIP(hipSetDevice(ctx->device));
-    ctx->n = 0;
-    ctx->h_start = 0.0;
-    NWK_HIP(ctx->cloud.ensure(sizeof(float) * 3 * (size_t)n));
-    NWK_HIP(hipMemcpyAsync(ctx->cloud.p, xyz, sizeof(float) * 3 * (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-    bool finite[2];
-    NWK_HIP(bq::bounds<float>(ctx->stream, ctx->mm, ctx->cloud.as<float>(), (int)n, nullptr, 0, &ctx->g, finite));
-    if (!finite[0]) return fail(ctx, NWK_ERR_NONFINITE, "nwk_set_cloud: a localization is not finite");
-    ctx->n = (int)n;
+    const bq::CloudStatus s = ctx->grid.set_cloud(ctx->stream, xyz, n, on_device != 0);
+    if (!s.ok()) return bq::cloud_fail(ctx, "nwk_set_cloud", s, NWK_CODES);
     const int r = ensure_grid(ctx, INFINITY);
-    if (r != NWK_OK) ctx->n = 0;
+    if (r != NWK_OK) ctx->grid.n = 0;
     return r;
 }
 
@@ -215,7 +190,7 @@ NWK_EXPORT int nwk_kth_distance(nwk_ctx *ctx, const float *queries, int64_t nq, 
     if (!k_and_cap_ok(k, r_cap)) return NWK_ERR_BADARG;
     if (!queries_on_device && !bq::all_finite(queries, 3 * nq)) return fail(ctx, NWK_ERR_NONFINITE, "nwk_kth_distance: a query is not finite");
     if (!ctx) return NWK_ERR_BADARG;
-    if (ctx->n < 1) return fail(ctx, NWK_ERR_NOCLOUD, "nwk_kth_distance: nwk_set_cloud first");
+    if (ctx->grid.n < 1) return fail(ctx, NWK_ERR_NOCLOUD, "nwk_kth_distance: nwk_set_cloud first");
     NWK_HIP(hipSetDevice(ctx->device));
     const int r = ensure_grid(ctx, r_cap);
     if (r != NWK_OK) return r;
@@ -227,8 +202,8 @@ NWK_EXPORT int nwk_kth_distance(nwk_ctx *ctx, const float *queries, int64_t nq, 
     NWK_HIP(ctx->dist.ensure(sizeof(double) * (size_t)nq));
     NWK_HIP(ctx->flag.ensure(sizeof(int)));
     NWK_HIP(hipMemsetAsync(ctx->flag.p, 0, sizeof(int), ctx->stream));
-    hipLaunchKernelGGL(k_kn_queries, dim3(nblk(nq, NWK_BLOCK)), dim3(NWK_BLOCK), 0, ctx->stream, dq, (int)nq, ctx->sorted.as<float4>(), ctx->cstart.as<int>(),
-                       ctx->g, k, r_cap, r_cap * r_cap, ctx->dist.as<double>(), ctx->flag.as<int>());
+    hipLaunchKernelGGL(k_kn_queries, dim3(nblk(nq, NWK_BLOCK)), dim3(NWK_BLOCK), 0, ctx->stream, dq, (int)nq, ctx->grid.sorted.as<float4>(), ctx->grid.cstart.as<int>(),
+                       ctx->grid.g, k, r_cap, r_cap * r_cap, ctx->dist.as<double>(), ctx->flag.as<int>());
     NWK_HIP(hipGetLastError());
     int bad = 0;
     NWK_HIP(hipMemcpyAsync(&bad, ctx->flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -249,14 +224,14 @@ NWK_EXPORT int nwk_node_field(nwk_ctx *ctx, const float *lo, float h, const int3
     }
     if (nvox > (1ll << 30)) return NWK_ERR_BADARG;
     if (!ctx) return NWK_ERR_BADARG;
-    if (ctx->n < 1) return fail(ctx, NWK_ERR_NOCLOUD, "nwk_node_field: nwk_set_cloud first");
+    if (ctx->grid.n < 1) return fail(ctx, NWK_ERR_NOCLOUD, "nwk_node_field: nwk_set_cloud first");
     NWK_HIP(hipSetDevice(ctx->device));
     ctx->n_field = 0;
     const int r = ensure_grid(ctx, r_cap);
     if (r != NWK_OK) return r;
     NWK_HIP(ctx->field.ensure(sizeof(u64) * (size_t)nvox));
     hipLaunchKernelGGL(k_kn_nodes, dim3(nblk(nvox, NWK_BLOCK)), dim3(NWK_BLOCK), 0, ctx->stream, lo[0], lo[1], lo[2], h, dims[0], dims[1], dims[2],
-                       ctx->sorted.as<float4>(), ctx->cstart.as<int>(), ctx->g, k, r_cap, r_cap * r_cap, ctx->field.as<u64>());
+                       ctx->grid.sorted.as<float4>(), ctx->grid.cstart.as<int>(), ctx->grid.g, k, r_cap, r_cap * r_cap, ctx->field.as<u64>());
     NWK_HIP(hipGetLastError());
     if (field_host) NWK_HIP(hipMemcpyAsync(field_host, ctx->field.p, sizeof(u64) * (size_t)nvox, hipMemcpyDeviceToHost, ctx->stream));
     NWK_HIP(hipStreamSynchronize(ctx->stream));

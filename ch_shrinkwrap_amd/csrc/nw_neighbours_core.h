@@ -5,10 +5,12 @@
 //   - the lower bound of a ring of cells;
 //   - the quantisation of a node's value into the uint64 field nwi_extract reads.
 // Nothing may be contracted into an fma: compile with -ffp-contract=off.  No HIP header is needed: without a HIP compiler NWK_HD is
-// plain `inline`.
+// plain `inline`.  nw_bq_core.h (HIP-free as well) is included for the cores on top of this one: bq::PtF32, the cloud point in cell order.
 #pragma once
 #include <cmath>
 #include <cstdint>
+
+#include "nw_bq_core.h"
 
 #if defined(__HIPCC__)
 #define NWK_HD __host__ __device__ __forceinline__

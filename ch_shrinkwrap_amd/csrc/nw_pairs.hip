@@ -1,8 +1,7 @@
 // Exact pair-distance counts of a localization cloud on the device (MI355X, gfx950): include/nw_pairs.h.
 //
-//   (bq::bounds, bq::size_grid, bq::build_grid)   the query units' shared point grid in float: bounding box and finiteness of the cloud,
-//                                     cell of every point and the cells' starts
-//   k_pq_order       the cloud in cell order with every point's index in the caller's array (the shared scatter keeps coordinates only)
+//   (bq::CloudGrid: set_cloud, bin)   the cloud query units' shared cloud grid in float (nw_bq.h): bounding box and finiteness of the
+//                                     cloud, the cloud in cell order with every point's index in the caller's array, the cells' starts
 //   k_pq_pairs<W>    one lane per query (auto mode: the cloud's points in cell order; cross mode: the caller's order): the walk of
 //                    nwq_walk, every visited point's bin, the lane's m counters in a column of LDS ([bin][lane], uint32: the column
 //                    stride is the workgroup's size, so a wave's increments never share a bank whatever their bins are, and nothing
@@ -17,7 +16,7 @@
 // edges.  With either size the LDS lets the same number of waves onto a CU.
 //
 // The definition -- the edges, the bin, the walk with its proof -- is csrc/nw_pairs_core.h, which the tests also compile for the CPU.
-// The device buffer, the point grid and the context's scaffolding are the query units' shared ones (nw_bq.h).
+// The device buffer, the cloud grid and the context's scaffolding are the query units' shared ones (nw_bq.h).
 // All stores are vector stores; no kernel uses scratch (build.py's KERNEL_BUDGETS checks it).
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -31,7 +30,7 @@
 #include "nw_pairs_core.h"
 
 #define NWQ_EXPORT extern "C" __attribute__((visibility("default")))
-#define NWQ_BLOCK 256               // k_pq_order, k_pq_totals
+#define NWQ_BLOCK 256               // k_pq_totals
 #define NWQ_LANES_NARROW 128
 #define NWQ_LANES_WIDE 64
 // a workgroup's two counters beside its row of bins
@@ -46,18 +45,6 @@ typedef unsigned int u32;
 struct pq_edges {
     double e2[NWQ_NARROW_BINS];
 };
-
-__global__ __launch_bounds__(NWQ_BLOCK) void k_pq_order(const float *__restrict__ xyz, int n, const int *__restrict__ cell, int *__restrict__ cursor,
-                                                        nwq_pt *__restrict__ pts)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int slot = atomicAdd(&cursor[cell[i]], 1);          // (order inside a cell is arbitrary: no output depends on it)
-    if (slot < 0 || slot >= n) return;                        // (cannot happen: the cursors start at the scan of the counts)
-    nwq_pt p;
-    p.x = xyz[3 * (int64_t)i]; p.y = xyz[3 * (int64_t)i + 1]; p.z = xyz[3 * (int64_t)i + 2]; p.i = i;
-    pts[slot] = p;
-}
 
 // what a lane does with a visited point: its bin, one increment in the lane's column
 template <bool WIDE> struct pq_visit {
@@ -193,12 +180,7 @@ using bq::DevBuf;
 using bq::fail;
 
 struct nwq_ctx : bq::Ctx {
-    // the cloud (nwq_set_cloud) and its box
-    int n = 0;
-    DevBuf cloud, mm;
-    bq::Grid<float> g{};
-    double h_start = 0.0;               // the cell size the grid at hand was sized from (0: none)
-    DevBuf cell, cursor, cstart, sorted, scan_tmp, pts;
+    bq::CloudGrid grid;                 // the cloud (nwq_set_cloud), its box and its cells
     // the edges (nwq_set_edges): m = 0 until then
     int m = 0;
     double radii[NWQ_MAX_BINS], e2[NWQ_MAX_BINS];
@@ -213,45 +195,11 @@ namespace {
 
 #define NWQ_HIP(call) BQ_HIP(call, NWQ_ERR_NOMEM, NWQ_ERR_HIP)
 
-// at most max(2 n, 65536) cells, up to 2^26; at most 1025 an axis (NWK_CELL_SLACK rests on it); 400 widening steps
-const bq::GridRule NWQ_GRID_RULE = {2, 1ll << 26, 1025, 400};
+const bq::CloudCodes NWQ_CODES = {NWQ_ERR_BADARG, NWQ_ERR_NONFINITE, NWQ_ERR_NOMEM, NWQ_ERR_HIP};
 
-// the cell size a count starts from: NWQ_CELL_OF_RMAX of the largest radius, never below 1/1024 of the widest axis (the walk's proof
-// needs it); a cloud without extent and a zero radius get one cell of side 1
-double starting_cell(const nwq_ctx *ctx, double r_max)
-{
-    double emax = 0.0;
-    for (int d = 0; d < 3; ++d) emax = std::max(emax, (double)ctx->g.hi[d] - (double)ctx->g.lo[d]);
-    double h = std::max(ctx->cell_of_rmax * r_max, emax / 1024.0);
-    if (!((float)h > 0.0f) || !std::isfinite((float)h)) h = (emax > 0.0 && std::isfinite((float)emax)) ? emax : 1.0;
-    return h;
-}
-
-// the grid for edges with this largest radius: the one at hand if it was sized from the same starting cell, else the cloud binned anew
-int ensure_grid(nwq_ctx *ctx, double r_max)
-{
-    const double h0 = starting_cell(ctx, r_max);
-    if (ctx->h_start == h0) return NWQ_OK;
-    ctx->h_start = 0.0;
-    double ext[3];
-    for (int d = 0; d < 3; ++d) ext[d] = (double)ctx->g.hi[d] - (double)ctx->g.lo[d];
-    double h = h0;
-    if (!bq::size_grid(NWQ_GRID_RULE, ctx->n, ext, &h, ctx->g.dims)) return fail(ctx, NWQ_ERR_BADARG, "nwq: no cell size keeps the grid within its cap");
-    ctx->g.h = (float)h;
-    if (!(ctx->g.h > 0.0f) || !std::isfinite(ctx->g.h)) return fail(ctx, NWQ_ERR_BADARG, "nwq: the cell size is not a positive float");
-    int total = -1;
-    NWQ_HIP(bq::build_grid<float>(ctx->stream, ctx->cloud.as<float>(), ctx->n, ctx->g, ctx->cell, ctx->cursor, ctx->scan_tmp, ctx->cstart, ctx->sorted, &total));
-    if (total != ctx->n) return fail(ctx, NWQ_ERR_HIP, "nwq: the cell counts do not add up to the cloud");
-    // the same order once more, with the indices
-    NWQ_HIP(ctx->pts.ensure(sizeof(nwq_pt) * (size_t)ctx->n));
-    NWQ_HIP(hipMemcpyAsync(ctx->cursor.p, ctx->cstart.p, sizeof(int) * (size_t)ctx->g.cells(), hipMemcpyDeviceToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_pq_order, dim3(bq::nblk(ctx->n, NWQ_BLOCK)), dim3(NWQ_BLOCK), 0, ctx->stream, ctx->cloud.as<float>(), ctx->n, ctx->cell.as<int>(),
-                       ctx->cursor.as<int>(), ctx->pts.as<nwq_pt>());
-    NWQ_HIP(hipGetLastError());
-    NWQ_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->h_start = h0;
-    return NWQ_OK;
-}
+// the cell size a count starts from: NWQ_CELL_OF_RMAX of the largest radius (bq::cloud_cell); a cloud without extent and a zero radius
+// get one cell of side 1
+double starting_cell(const nwq_ctx *ctx, double r_max) { return bq::cloud_cell(ctx->cell_of_rmax * r_max, ctx->grid.emax()); }
 
 }  // namespace
 
@@ -276,20 +224,13 @@ NWQ_EXPORT int nwq_set_cloud(nwq_ctx *ctx, const float *xyz, int64_t n, int on_d
 {
     if (!xyz || n < 1 || n > NWQ_MAX_N || (on_device != 0 && on_device != 1)) return NWQ_ERR_BADARG;
     if (!on_device && !bq::all_finite(xyz, 3 * n)) {
-        if (ctx) { ctx->n = 0; ctx->h_start = 0.0; }              // (a failed call leaves no cloud, whichever check failed)
+        if (ctx) ctx->grid.forget();                              // (a failed call leaves no cloud, whichever check failed)
         return fail(ctx, NWQ_ERR_NONFINITE, "nwq_set_cloud: a localization is not finite");
     }
     if (!ctx) return NWQ_ERR_BADARG;
     NWQ_HIP(hipSetDevice(ctx->device));
-    ctx->n = 0;
-    ctx->h_start = 0.0;
-    NWQ_HIP(ctx->cloud.ensure(sizeof(float) * 3 * (size_t)n));
-    NWQ_HIP(hipMemcpyAsync(ctx->cloud.p, xyz, sizeof(float) * 3 * (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-    bool finite[2];
-    NWQ_HIP(bq::bounds<float>(ctx->stream, ctx->mm, ctx->cloud.as<float>(), (int)n, nullptr, 0, &ctx->g, finite));
-    if (!finite[0]) return fail(ctx, NWQ_ERR_NONFINITE, "nwq_set_cloud: a localization is not finite");
-    ctx->n = (int)n;
-    return NWQ_OK;
+    const bq::CloudStatus s = ctx->grid.set_cloud(ctx->stream, xyz, n, on_device != 0);
+    return s.ok() ? NWQ_OK : bq::cloud_fail(ctx, "nwq_set_cloud", s, NWQ_CODES);
 }
 
 NWQ_EXPORT int nwq_set_edges(nwq_ctx *ctx, const double *radii, int64_t m)
@@ -309,16 +250,17 @@ NWQ_EXPORT int nwq_count(nwq_ctx *ctx, const float *queries, int64_t nq, int on_
     if (queries ? (nq < 1 || nq > NWQ_MAX_N) : nq < 0) return NWQ_ERR_BADARG;
     if (queries && !on_device && !bq::all_finite(queries, 3 * nq)) return fail(ctx, NWQ_ERR_NONFINITE, "nwq_count: a query is not finite");
     if (!ctx) return NWQ_ERR_BADARG;
-    if (ctx->n < 1) return fail(ctx, NWQ_ERR_NOCLOUD, "nwq_count: nwq_set_cloud first");
+    if (ctx->grid.n < 1) return fail(ctx, NWQ_ERR_NOCLOUD, "nwq_count: nwq_set_cloud first");
     if (ctx->m < 1) return fail(ctx, NWQ_ERR_NOCLOUD, "nwq_count: nwq_set_edges first");
-    if (!queries && nq != 0 && nq != ctx->n) return fail(ctx, NWQ_ERR_BADARG, "nwq_count: without queries nq is 0 or the cloud's n");
+    if (!queries && nq != 0 && nq != ctx->grid.n) return fail(ctx, NWQ_ERR_BADARG, "nwq_count: without queries nq is 0 or the cloud's n");
     NWQ_HIP(hipSetDevice(ctx->device));
     const int m = ctx->m;
     const double r_max = ctx->radii[m - 1], r_max2 = ctx->e2[m - 1];
-    const int r = ensure_grid(ctx, r_max);
-    if (r != NWQ_OK) return r;
+    const bq::CloudStatus binned = ctx->grid.bin(ctx->stream, starting_cell(ctx, r_max));
+    if (!binned.ok()) return bq::cloud_fail(ctx, "nwq", binned, NWQ_CODES);
+    const bq::Grid<float> &g = ctx->grid.g;
     hipStream_t st = ctx->stream;
-    const int n_queries = queries ? (int)nq : ctx->n;
+    const int n_queries = queries ? (int)nq : ctx->grid.n;
     const bool wide = m > NWQ_NARROW_BINS;
     const int lanes = wide ? NWQ_LANES_WIDE : NWQ_LANES_NARROW, bins = wide ? NWQ_MAX_BINS : NWQ_NARROW_BINS;
     const int nb = bq::nblk(n_queries, lanes);
@@ -346,16 +288,16 @@ NWQ_EXPORT int nwq_count(nwq_ctx *ctx, const float *queries, int64_t nq, int on_
     NWQ_HIP(hipMemsetAsync(ctx->flag.p, 0, sizeof(int), st));
 
     nwq_grid G;
-    for (int d = 0; d < 3; ++d) { G.lo[d] = (double)ctx->g.lo[d]; G.hi[d] = (double)ctx->g.hi[d]; G.dims[d] = ctx->g.dims[d]; }
-    G.h = (double)ctx->g.h;
+    for (int d = 0; d < 3; ++d) { G.lo[d] = (double)g.lo[d]; G.hi[d] = (double)g.hi[d]; G.dims[d] = g.dims[d]; }
+    G.h = (double)g.h;
     pq_edges E;
     for (int b = 0; b < NWQ_NARROW_BINS; ++b) E.e2[b] = ctx->e2[b];
     u32 *dlocal = local ? ctx->local.as<u32>() : nullptr;
     if (wide)
-        hipLaunchKernelGGL(k_pq_pairs<true>, dim3(nb), dim3(lanes), 0, st, dq, n_queries, ctx->pts.as<nwq_pt>(), ctx->cstart.as<int>(), G, E, ctx->e2_dev.as<double>(),
+        hipLaunchKernelGGL(k_pq_pairs<true>, dim3(nb), dim3(lanes), 0, st, dq, n_queries, ctx->grid.sorted.as<nwq_pt>(), ctx->grid.cstart.as<int>(), G, E, ctx->e2_dev.as<double>(),
                            m, r_max, r_max2, dlocal, ctx->part_hist.as<u64>(), ctx->part_cnt.as<u64>(), ctx->flag.as<int>());
     else
-        hipLaunchKernelGGL(k_pq_pairs<false>, dim3(nb), dim3(lanes), 0, st, dq, n_queries, ctx->pts.as<nwq_pt>(), ctx->cstart.as<int>(), G, E, ctx->e2_dev.as<double>(),
+        hipLaunchKernelGGL(k_pq_pairs<false>, dim3(nb), dim3(lanes), 0, st, dq, n_queries, ctx->grid.sorted.as<nwq_pt>(), ctx->grid.cstart.as<int>(), G, E, ctx->e2_dev.as<double>(),
                            m, r_max, r_max2, dlocal, ctx->part_hist.as<u64>(), ctx->part_cnt.as<u64>(), ctx->flag.as<int>());
     hipLaunchKernelGGL(k_pq_totals, dim3(1), dim3(NWQ_BLOCK), 0, st, ctx->part_hist.as<u64>(), ctx->part_cnt.as<u64>(), (int64_t)nb, bins, ctx->totals.as<u64>());
     NWQ_HIP(hipGetLastError());
@@ -374,10 +316,10 @@ NWQ_EXPORT int nwq_count(nwq_ctx *ctx, const float *queries, int64_t nq, int on_
     info[NWQ_INFO_TESTS] = (int64_t)tot[NWQ_MAX_BINS + NWQ_C_TESTS];
     info[NWQ_INFO_CELLS_READ] = (int64_t)tot[NWQ_MAX_BINS + NWQ_C_CELLS];
     info[NWQ_INFO_CELL_SIZE] = __builtin_bit_cast(int64_t, G.h);
-    info[NWQ_INFO_CELLS] = ctx->g.cells();
+    info[NWQ_INFO_CELLS] = g.cells();
     info[NWQ_INFO_VARIANT] = wide ? 1 : 0;
     info[NWQ_INFO_N_QUERIES] = n_queries;
-    info[NWQ_INFO_N_CLOUD] = ctx->n;
+    info[NWQ_INFO_N_CLOUD] = ctx->grid.n;
     info[NWQ_INFO_BINS] = m;
     return NWQ_OK;
 }

@@ -19,11 +19,8 @@
 // ball more closely and reads more cells, a larger one reads fewer cells and tests more points that are too far.
 #define NWQ_CELL_OF_RMAX 0.5
 
-// a cloud point in cell order: its coordinates and its index in the caller's array
-struct alignas(16) nwq_pt {
-    float x, y, z;
-    int i;
-};
+// a cloud point in cell order: its coordinates and its index in the caller's array (the cloud grid's, nw_bq_core.h)
+typedef bq::PtF32 nwq_pt;
 
 // d2 of a pair, p = the cloud point, (x, y, z) = (double) query.  (ex * ex + ey * ey) + ez * ez is the same number with the two points
 // swapped: the differences are each other's negations, exactly.  In auto mode (i, j) and (j, i) therefore fall into the same bin.

@@ -1,8 +1,7 @@
 // The local shape of a localization cloud on the device (MI355X, gfx950): include/nw_structure.h.
 //
-//   (bq::bounds, bq::size_grid, bq::build_grid)   the query units' shared point grid in float: bounding box and finiteness of the cloud,
-//                                     cell of every point and the cells' starts
-//   k_st_order       the cloud in cell order with every point's index in the caller's array (the shared scatter keeps coordinates only)
+//   (bq::CloudGrid: set_cloud, bin)   the cloud query units' shared cloud grid in float (nw_bq.h): bounding box and finiteness of the
+//                                     cloud, the cloud in cell order with every point's index in the caller's array, the cells' starts
 //   k_st_moments     one lane per query (auto mode: the cloud's points in cell order, so a wave's boxes overlap and its lanes read the same
 //                    cells; cross mode: the caller's order): the walk of nwf_walk, every visited point's inclusive test, a neighbour's
 //                    three quantised offsets and their six products into ten 64-bit sums held in registers -- no LDS column, no atomics on
@@ -12,7 +11,7 @@
 //   k_st_totals      the workgroups' counters, one workgroup; integer sums in a fixed order
 //
 // The definition -- the neighbourhood, the quantisation, the moments, the float64 procedure, the walk with its proof -- is
-// csrc/nw_structure_core.h, which the tests also compile for the CPU.  The device buffer, the point grid and the context's scaffolding are
+// csrc/nw_structure_core.h, which the tests also compile for the CPU.  The device buffer, the cloud grid and the context's scaffolding are
 // the query units' shared ones (nw_bq.h).  All stores are vector stores; no kernel uses scratch (build.py's KERNEL_BUDGETS checks it).
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -26,7 +25,7 @@
 #include "nw_structure_core.h"
 
 #define NWF_EXPORT extern "C" __attribute__((visibility("default")))
-#define NWF_BLOCK 256               // k_st_order, k_st_eigen, k_st_totals
+#define NWF_BLOCK 256               // k_st_eigen, k_st_totals
 #define NWF_LANES 128               // k_st_moments
 // a workgroup's counters
 #define NWF_COUNTERS 4
@@ -36,18 +35,6 @@
 #define NWF_C_FEW 3
 
 typedef unsigned long long u64;
-
-__global__ __launch_bounds__(NWF_BLOCK) void k_st_order(const float *__restrict__ xyz, int n, const int *__restrict__ cell, int *__restrict__ cursor,
-                                                        nwf_pt *__restrict__ pts)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int slot = atomicAdd(&cursor[cell[i]], 1);          // (order inside a cell is arbitrary: no output depends on it)
-    if (slot < 0 || slot >= n) return;                        // (cannot happen: the cursors start at the scan of the counts)
-    nwf_pt p;
-    p.x = xyz[3 * (int64_t)i]; p.y = xyz[3 * (int64_t)i + 1]; p.z = xyz[3 * (int64_t)i + 2]; p.i = i;
-    pts[slot] = p;
-}
 
 // what a lane does with a visited point: the test, and a neighbour's terms into the lane's ten sums
 struct st_visit {
@@ -175,12 +162,7 @@ using bq::DevBuf;
 using bq::fail;
 
 struct nwf_ctx : bq::Ctx {
-    // the cloud (nwf_set_cloud) and its box
-    int n = 0;
-    DevBuf cloud, mm;
-    bq::Grid<float> g{};
-    double h_start = 0.0;               // the cell size the grid at hand was sized from (0: none)
-    DevBuf cell, cursor, cstart, sorted, scan_tmp, pts;
+    bq::CloudGrid grid;                 // the cloud (nwf_set_cloud), its box and its cells
     // one query
     DevBuf q, moments, eigenvalues, vectors, flags, part, totals, flag;
 };
@@ -189,45 +171,10 @@ namespace {
 
 #define NWF_HIP(call) BQ_HIP(call, NWF_ERR_NOMEM, NWF_ERR_HIP)
 
-// at most max(2 n, 65536) cells, up to 2^26; at most 1025 an axis (NWK_CELL_SLACK rests on it); 400 widening steps
-const bq::GridRule NWF_GRID_RULE = {2, 1ll << 26, 1025, 400};
+const bq::CloudCodes NWF_CODES = {NWF_ERR_BADARG, NWF_ERR_NONFINITE, NWF_ERR_NOMEM, NWF_ERR_HIP};
 
-// the cell size a query starts from: NWF_CELL_OF_R of the radius, never below 1/1024 of the widest axis (the walk's proof needs it); a
-// cell size that is no positive float gives way to the extent, a cloud without extent gets one cell of side 1
-double starting_cell(const nwf_ctx *ctx, double r)
-{
-    double emax = 0.0;
-    for (int d = 0; d < 3; ++d) emax = std::max(emax, (double)ctx->g.hi[d] - (double)ctx->g.lo[d]);
-    double h = std::max(NWF_CELL_OF_R * r, emax / 1024.0);
-    if (!((float)h > 0.0f) || !std::isfinite((float)h)) h = (emax > 0.0 && std::isfinite((float)emax)) ? emax : 1.0;
-    return h;
-}
-
-// the grid for this radius: the one at hand if it was sized from the same starting cell, else the cloud binned anew
-int ensure_grid(nwf_ctx *ctx, double r)
-{
-    const double h0 = starting_cell(ctx, r);
-    if (ctx->h_start == h0) return NWF_OK;
-    ctx->h_start = 0.0;
-    double ext[3];
-    for (int d = 0; d < 3; ++d) ext[d] = (double)ctx->g.hi[d] - (double)ctx->g.lo[d];
-    double h = h0;
-    if (!bq::size_grid(NWF_GRID_RULE, ctx->n, ext, &h, ctx->g.dims)) return fail(ctx, NWF_ERR_BADARG, "nwf: no cell size keeps the grid within its cap");
-    ctx->g.h = (float)h;
-    if (!(ctx->g.h > 0.0f) || !std::isfinite(ctx->g.h)) return fail(ctx, NWF_ERR_BADARG, "nwf: the cell size is not a positive float");
-    int total = -1;
-    NWF_HIP(bq::build_grid<float>(ctx->stream, ctx->cloud.as<float>(), ctx->n, ctx->g, ctx->cell, ctx->cursor, ctx->scan_tmp, ctx->cstart, ctx->sorted, &total));
-    if (total != ctx->n) return fail(ctx, NWF_ERR_HIP, "nwf: the cell counts do not add up to the cloud");
-    // the same order once more, with the indices
-    NWF_HIP(ctx->pts.ensure(sizeof(nwf_pt) * (size_t)ctx->n));
-    NWF_HIP(hipMemcpyAsync(ctx->cursor.p, ctx->cstart.p, sizeof(int) * (size_t)ctx->g.cells(), hipMemcpyDeviceToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_st_order, dim3(bq::nblk(ctx->n, NWF_BLOCK)), dim3(NWF_BLOCK), 0, ctx->stream, ctx->cloud.as<float>(), ctx->n, ctx->cell.as<int>(),
-                       ctx->cursor.as<int>(), ctx->pts.as<nwf_pt>());
-    NWF_HIP(hipGetLastError());
-    NWF_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->h_start = h0;
-    return NWF_OK;
-}
+// the cell size a query starts from: NWF_CELL_OF_R of the radius (bq::cloud_cell)
+double starting_cell(const nwf_ctx *ctx, double r) { return bq::cloud_cell(NWF_CELL_OF_R * r, ctx->grid.emax()); }
 
 }  // namespace
 
@@ -243,20 +190,13 @@ NWF_EXPORT int nwf_set_cloud(nwf_ctx *ctx, const float *xyz, int64_t n, int on_d
 {
     if (!xyz || n < 1 || n > NWF_MAX_N || (on_device != 0 && on_device != 1)) return NWF_ERR_BADARG;
     if (!on_device && !bq::all_finite(xyz, 3 * n)) {
-        if (ctx) { ctx->n = 0; ctx->h_start = 0.0; }              // (a failed call leaves no cloud, whichever check failed)
+        if (ctx) ctx->grid.forget();                              // (a failed call leaves no cloud, whichever check failed)
         return fail(ctx, NWF_ERR_NONFINITE, "nwf_set_cloud: a localization is not finite");
     }
     if (!ctx) return NWF_ERR_BADARG;
     NWF_HIP(hipSetDevice(ctx->device));
-    ctx->n = 0;
-    ctx->h_start = 0.0;
-    NWF_HIP(ctx->cloud.ensure(sizeof(float) * 3 * (size_t)n));
-    NWF_HIP(hipMemcpyAsync(ctx->cloud.p, xyz, sizeof(float) * 3 * (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-    bool finite[2];
-    NWF_HIP(bq::bounds<float>(ctx->stream, ctx->mm, ctx->cloud.as<float>(), (int)n, nullptr, 0, &ctx->g, finite));
-    if (!finite[0]) return fail(ctx, NWF_ERR_NONFINITE, "nwf_set_cloud: a localization is not finite");
-    ctx->n = (int)n;
-    return NWF_OK;
+    const bq::CloudStatus s = ctx->grid.set_cloud(ctx->stream, xyz, n, on_device != 0);
+    return s.ok() ? NWF_OK : bq::cloud_fail(ctx, "nwf_set_cloud", s, NWF_CODES);
 }
 
 NWF_EXPORT int nwf_query(nwf_ctx *ctx, const float *queries, int64_t nq, int on_device, double r, const double *viewpoint, int64_t *moments,
@@ -269,13 +209,14 @@ NWF_EXPORT int nwf_query(nwf_ctx *ctx, const float *queries, int64_t nq, int on_
     if (viewpoint && !bq::all_finite(viewpoint, 3)) return fail(ctx, NWF_ERR_NONFINITE, "nwf_query: the viewpoint is not finite");
     if (queries && !on_device && !bq::all_finite(queries, 3 * nq)) return fail(ctx, NWF_ERR_NONFINITE, "nwf_query: a query is not finite");
     if (!ctx) return NWF_ERR_BADARG;
-    if (ctx->n < 1) return fail(ctx, NWF_ERR_NOCLOUD, "nwf_query: nwf_set_cloud first");
-    if (!queries && nq != 0 && nq != ctx->n) return fail(ctx, NWF_ERR_BADARG, "nwf_query: without queries nq is 0 or the cloud's n");
+    if (ctx->grid.n < 1) return fail(ctx, NWF_ERR_NOCLOUD, "nwf_query: nwf_set_cloud first");
+    if (!queries && nq != 0 && nq != ctx->grid.n) return fail(ctx, NWF_ERR_BADARG, "nwf_query: without queries nq is 0 or the cloud's n");
     NWF_HIP(hipSetDevice(ctx->device));
-    const int rc = ensure_grid(ctx, r);
-    if (rc != NWF_OK) return rc;
+    const bq::CloudStatus binned = ctx->grid.bin(ctx->stream, starting_cell(ctx, r));
+    if (!binned.ok()) return bq::cloud_fail(ctx, "nwf", binned, NWF_CODES);
+    const bq::Grid<float> &g = ctx->grid.g;
     hipStream_t st = ctx->stream;
-    const int n_queries = queries ? (int)nq : ctx->n;
+    const int n_queries = queries ? (int)nq : ctx->grid.n;
     const int nb = bq::nblk(n_queries, NWF_LANES);
     double s = 0.0, step = 0.0;
     nwf_scale(r, &s, &step);
@@ -301,14 +242,14 @@ NWF_EXPORT int nwf_query(nwf_ctx *ctx, const float *queries, int64_t nq, int on_
     }
 
     nwf_grid G;
-    for (int d = 0; d < 3; ++d) { G.lo[d] = (double)ctx->g.lo[d]; G.hi[d] = (double)ctx->g.hi[d]; G.dims[d] = ctx->g.dims[d]; }
-    G.h = (double)ctx->g.h;
-    hipLaunchKernelGGL(k_st_moments, dim3(nb), dim3(NWF_LANES), 0, st, dq, n_queries, ctx->pts.as<nwf_pt>(), ctx->cstart.as<int>(), G, r, r2, s,
+    for (int d = 0; d < 3; ++d) { G.lo[d] = (double)g.lo[d]; G.hi[d] = (double)g.hi[d]; G.dims[d] = g.dims[d]; }
+    G.h = (double)g.h;
+    hipLaunchKernelGGL(k_st_moments, dim3(nb), dim3(NWF_LANES), 0, st, dq, n_queries, ctx->grid.sorted.as<nwf_pt>(), ctx->grid.cstart.as<int>(), G, r, r2, s,
                        ctx->moments.as<long long>(), ctx->part.as<u64>(), ctx->flag.as<int>());
     hipLaunchKernelGGL(k_st_totals, dim3(1), dim3(NWF_BLOCK), 0, st, ctx->part.as<u64>(), (int64_t)nb, ctx->totals.as<u64>());
     if (shape)
         hipLaunchKernelGGL(k_st_eigen, dim3(bq::nblk(n_queries, NWF_BLOCK)), dim3(NWF_BLOCK), 0, st, ctx->moments.as<long long>(),
-                           dq ? dq : ctx->cloud.as<float>(), n_queries, step, viewpoint ? 1 : 0, viewpoint ? viewpoint[0] : 0.0, viewpoint ? viewpoint[1] : 0.0,
+                           dq ? dq : ctx->grid.cloud.as<float>(), n_queries, step, viewpoint ? 1 : 0, viewpoint ? viewpoint[0] : 0.0, viewpoint ? viewpoint[1] : 0.0,
                            viewpoint ? viewpoint[2] : 0.0, ctx->eigenvalues.as<double>(), ctx->vectors.as<double>(), ctx->flags.as<unsigned char>());
     NWF_HIP(hipGetLastError());
 
@@ -327,10 +268,10 @@ NWF_EXPORT int nwf_query(nwf_ctx *ctx, const float *queries, int64_t nq, int on_
     info[NWF_INFO_TESTS] = (int64_t)tot[NWF_C_TESTS];
     info[NWF_INFO_CELLS_READ] = (int64_t)tot[NWF_C_CELLS];
     info[NWF_INFO_CELL_SIZE] = __builtin_bit_cast(int64_t, G.h);
-    info[NWF_INFO_CELLS] = ctx->g.cells();
+    info[NWF_INFO_CELLS] = g.cells();
     info[NWF_INFO_NEIGHBOURS] = (int64_t)tot[NWF_C_NEIGHBOURS];
     info[NWF_INFO_FEW] = (int64_t)tot[NWF_C_FEW];
     info[NWF_INFO_N_QUERIES] = n_queries;
-    info[NWF_INFO_N_CLOUD] = ctx->n;
+    info[NWF_INFO_N_CLOUD] = ctx->grid.n;
     return NWF_OK;
 }

@@ -35,11 +35,8 @@
 #define NWF_FLAG_POINT 8            // n >= 3 and lambda_0 <= 0: all neighbours in one place (as far as the quantisation sees)
 #define NWF_FLAG_TURNED 16          // the viewpoint turned the normal against the largest-component rule
 
-// a cloud point in cell order: its coordinates and its index in the caller's array
-struct alignas(16) nwf_pt {
-    float x, y, z;
-    int i;
-};
+// a cloud point in cell order: its coordinates and its index in the caller's array (the cloud grid's, nw_bq_core.h)
+typedef bq::PtF32 nwf_pt;
 
 // Whether r is a radius: finite, 0 < r <= 2^40, and *r2 = r * r (float64, computed here once) finite and above 0.  A nan fails the first
 // comparison.

@@ -48,14 +48,7 @@ def load():
 
 
 _p = _lib.ptr
-
-
-def _cloud(points):
-    """-> (what keeps the memory alive, pointer, n, on_device): an (n,3) array (copied to float32 if it is not) or (device pointer, n)"""
-    if isinstance(points, tuple) and len(points) == 2 and isinstance(points[0], (int, np.integer)):
-        return None, _p(int(points[0])), int(points[1]), 1
-    a = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
-    return a, _p(a), a.shape[0], 0
+_cloud = _lib.cloud_f32
 
 
 class NeighbourContext(_lib.QueryContext):

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = ['k_st_order', 'k_st_moments', 'k_st_eigen', 'k_st_totals']
+KERNELS = ['k_st_moments', 'k_st_eigen', 'k_st_totals']
 
 
 def _declared():
@@ -90,8 +90,12 @@ def test_the_unit_is_new_and_the_core_reuses_the_neighbour_core():
     src = open(os.path.join(ROOT, 'ch_shrinkwrap_amd', 'csrc', 'nw_structure.hip')).read()
     code = re.sub(r'//.*', '', src)
     assert '"nw_structure_core.h"' in src and '"nw_bq.h"' in src and '"nw_neighbours.h"' not in src and '"nw_pairs_core.h"' not in src
-    assert 'bq::build_grid<float>' in code and 'bq::bounds<float>' in code and 'nwf_walk(' in code and 'nwf_visit(' in code and 'nwf_shape(' in code
-    assert 'atomicAdd' not in code.replace('atomicAdd(&cursor[cell[i]], 1)', '') and 'atomicCAS' not in code     # the results need no atomics
+    assert 'bq::CloudGrid grid;' in code and 'grid.set_cloud(' in code and 'grid.bin(' in code and 'nwf_walk(' in code and 'nwf_visit(' in code and 'nwf_shape(' in code
+    assert 'build_grid' not in code and 'bq::bounds' not in code and 'cursor' not in code                # the unit holds the cloud grid ...
+    shared = re.sub(r'//.*', '', open(os.path.join(ROOT, 'ch_shrinkwrap_amd', 'csrc', 'nw_bq.hip')).read())
+    assert 'build_grid<float>(stream, cloud.as<float>()' in shared and 'bounds<float>(stream, mm, cloud.as<float>()' in shared     # ... which bins with the shared grid
+    assert shared.count('atomicAdd(&cursor[cell[i]], 1)') == 1 and 'sorted[slot] = point_of(xyz + 3 * (int64_t)i, i)' in shared     # the one scatter, index and all
+    assert 'atomicAdd' not in code and 'atomicCAS' not in code                                           # the unit has no scatter of its own, and the results need no atomics
     for obj in build.BUDGETED_OBJECTS:
         names = build.kernel_resources(obj)
         if obj == build.OBJ_STRUCTURE:
